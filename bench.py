@@ -8,9 +8,9 @@ N -- so the N = 1, 2, 4, 8 lines of a scaling run measure the same frame.
 With N > 1 GPUs the frame is tile-sharded by interleaved row bands, the step
 including the single gather (RCCL over xGMI) to rank 0 and the un-shard.
 value = whole-frame samples / max-over-ranks time (strong scaling: the frame
-is fixed).  At N > 1 rank 0 first renders the same frame alone (untimed for
-`value`) and the line carries t1_ms and efficiency = T1 / (N * T_N) of this
-run, so the scaling line is self-contained.  --workload c1..c5 picks another
+is fixed).  At N > 1 with --full rank 0 first renders the same frame alone
+(untimed for `value`) and the line carries t1_ms and efficiency = T1 / (N * T_N)
+of this run, so the scaling line is self-contained.  --workload c1..c5 picks another
 BASELINE.json config (C4: box 3840x2160x4096spp); the line's metric string
 then names the frame actually rendered.  Every N > 1 line carries what the
 RCCL group actually was -- rccl_ranks (ncclCommCount of every communicator),
@@ -40,7 +40,22 @@ Efficiency = T1 / (N * T_N) with T1 and T_N timed the same way: wall clock
 per frame over the same kind of step (render + gather + un-shard), and again
 from the kernels' HIP events alone (efficiency_kernel).
 
-Also reported:
+A plain run sets up, renders --warmup untimed frames, times --steps frames,
+writes its outputs if --dump-outputs is given and prints the line: metric,
+value, ms_per_step (wall-clock milliseconds of one timed step), the frame's
+config and, at N > 1, the group.  --dump-outputs DIR writes the last timed
+step's image -- what a caller of the timed path holds after it -- as
+DIR/image.npy ([H, W, 3] float32, the reference's row order); the scene, the
+camera and the counter-RNG seed are fixed, so two runs with the same
+arguments render the same inputs.  A frame over the 64 MB limit (C4) is
+written as a fixed, seeded sample of its rows, DIR/image_rows.npy naming them.
+
+Everything else takes runs of its own and is reported with --full only: the
+untimed counting launch (the first warm-up frame then) and the kernels' HIP
+events behind `roofline` and `segments_per_s`, the per-rank times, T1 and the
+efficiencies at N > 1, and the CPU baseline with the quality rows.
+
+Reported with --full:
   roofline     -- VALU fp32 roofline of the render kernel: algorithmic FLOP
                   per launch (S_bar*(23*N_spheres + 100) + 60 per sample,
                   SURVEY.md 8(d), S_bar measured by the kernel's own segment
@@ -236,6 +251,32 @@ def cpu_baseline(scene_name, W, H, samps, nsub, threads, row_step, gpu_image=Non
     return out
 
 
+DUMP_LIMIT_BYTES = 60 * 10**6  # --dump-outputs: under 64 MB in all, the row list included
+DUMP_SEED = 0x5EED0001
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: `image` ([H, W, 3], the last timed step's frame) as
+    path/image.npy in float32.  A frame over DUMP_LIMIT_BYTES is written as a
+    sample of whole rows -- the same rows in every run (seeded), in ascending
+    order, their indices in path/image_rows.npy (float64).  Returns what was
+    written, for the line."""
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    os.makedirs(path, exist_ok=True)
+    info = {"dir": path, "image": {"shape": list(image.shape), "dtype": "float32", "rows": "all"}}
+    H = image.shape[0]
+    row_bytes = image.nbytes // max(H, 1)
+    if image.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(H, size=keep, replace=False))
+        image = np.ascontiguousarray(image[rows])
+        np.save(os.path.join(path, "image_rows.npy"), rows.astype(np.float64))
+        info["image"] = {"shape": list(image.shape), "dtype": "float32",
+                         "rows": f"{keep} of {H} (seeded sample, indices in image_rows.npy)"}
+    np.save(os.path.join(path, "image.npy"), image)
+    return info
+
+
 def resolve_launch(gpus, env):
     """(mode, world, rank, local) for --gpus and the launcher's environment:
     "single" (one GPU), "inprocess" (no launcher, --gpus N > 1: one process,
@@ -277,6 +318,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report what takes runs of its own: the counting launch and HIP events "
+                         "(roofline, segments_per_s, per-rank times), T1 / efficiency at N > 1, the CPU baseline "
+                         "and the quality rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's image to DIR/image.npy (float32 [H, W, 3]; "
+                         "a seeded sample of rows, listed in DIR/image_rows.npy, when over 64 MB)")
     ap.add_argument("--workload", choices=["auto"] + sorted(WORKLOADS), default="auto",
                     help="BASELINE.json config (auto = bench: the metric's box 1920x1080x1024spp frame, at every N; "
                          "c4: box 3840x2160x4096spp)")
@@ -490,6 +538,7 @@ def base_line(args, world, wl_name, scene, W, H, spp, samps, nsub, n_sph, elapse
         "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         "higher_is_better": True,
+        "full": bool(args.full),
         "scaling": "strong",
         "vs_baseline": None,
         "dtype": "f64 (reference-arithmetic mode)" if args.reference_f64 else "f32",
@@ -538,25 +587,46 @@ def run_inprocess(args):
         mc.close()
         log("error: the N-GPU group is not what the line would report: " + "; ".join(bad))
         sys.exit(3)
-    counters = mc.frame_device(cparams, counters=True)  # S_bar from the kernels' own counters (untimed)
-    seg_total, sph_total, box_total = (int(v) for v in counters[:3])
-    for _ in range(max(0, args.warmup - 1)):
+    full = args.full
+    warm = args.warmup
+    if full:  # S_bar from the kernels' own counters (untimed: the first warm-up frame)
+        counters = mc.frame_device(cparams, counters=True)
+        seg_total, sph_total, box_total = (int(v) for v in counters[:3])
+        warm -= 1
+    for _ in range(max(0, warm)):
         mc.frame_device(params)
     render_ms, frame_ms = [], []
     t0 = time.perf_counter()
     for _ in range(args.steps):
         mc.frame_device(params)  # synchronous: every device done, frame un-sharded on GPU 0
-        r, f = mc.frame_timing()
-        render_ms.append(r)
-        frame_ms.append(f)
+        if full:
+            r, f = mc.frame_timing()
+            render_ms.append(r)
+            frame_ms.append(f)
     elapsed = time.perf_counter() - t0
-    image_n = mc.image(params) if args.t1 == "auto" else None
+    want_t1 = full and args.t1 == "auto"
+    image_n = mc.image(params) if (want_t1 or args.dump_outputs) else None
     mc.close()
+    par = (f"tile-sharded row bands x{n}, one process (ptg_multi: ncclCommInitAll + ONE ncclGather per frame)"
+           + (f" -- REHEARSAL: {n} shards on one GPU, gathered by device copies" if rehearsal else ""))
+    value, out = base_line(args, n, wl_name, scene, W, H, spp, samps, nsub, n_sph, elapsed, par)
+    out["launch"] = "inprocess"
+    out["rccl_ranks"] = None if rehearsal else ranks
+    out["devices"] = [{"shard": k, "device": d, "pci_bus_id": b, "rccl_user_rank": u}
+                      for k, ((_, d, u), b) in enumerate(zip(info, bus))]
+    out["group_check"] = ("rehearsal: local shards, no RCCL communicator" if rehearsal else
+                          f"ok: {n} RCCL ranks per communicator on {len(set(devs))} distinct devices / "
+                          f"{len(set(bus))} PCI bus ids")
+    if args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, image_n)
+    if not full:
+        print(json.dumps(out), flush=True)
+        return
     render_ms = np.array(render_ms)  # [steps, n]
     kern_dev = render_ms.mean(0)  # per device
 
     t1 = None
-    if args.t1 == "auto":
+    if want_t1:
         m1 = ptgpu.MultiContext(scn, cam, [0], local_shards=1)
         m1.frame_device(params)  # warm-up
         k1 = max(1, args.t1_steps)
@@ -580,9 +650,6 @@ def run_inprocess(args):
     slow = int(np.argmax(kern_dev))
     s_bar, roof = roofline(frame_samples, seg_total, sph_total, box_total, dev_samples[slow], float(kern_dev[slow]),
                            n_sph, pmc)
-    par = (f"tile-sharded row bands x{n}, one process (ptg_multi: ncclCommInitAll + ONE ncclGather per frame)"
-           + (f" -- REHEARSAL: {n} shards on one GPU, gathered by device copies" if rehearsal else ""))
-    value, out = base_line(args, n, wl_name, scene, W, H, spp, samps, nsub, n_sph, elapsed, par)
     out["segments_per_s"] = round(value * 1e6 * s_bar, 1)
     out["roofline"] = roof
     with ptgpu.Context(scn, cam, device=0) as c0:
@@ -590,13 +657,6 @@ def run_inprocess(args):
     out["roofline"]["note"] = (f"achieved: the slowest device's kernel (device {devs[slow]}: its {dev_samples[slow]} "
                                f"samples over its HIP-event render time)")
     out["cpu_baseline"] = None
-    out["launch"] = "inprocess"
-    out["rccl_ranks"] = None if rehearsal else ranks
-    out["devices"] = [{"shard": k, "device": d, "pci_bus_id": b, "rccl_user_rank": u}
-                      for k, ((_, d, u), b) in enumerate(zip(info, bus))]
-    out["group_check"] = ("rehearsal: local shards, no RCCL communicator" if rehearsal else
-                          f"ok: {n} RCCL ranks per communicator on {len(set(devs))} distinct devices / "
-                          f"{len(set(bus))} PCI bus ids")
     out["per_rank"] = {"render_ms": [round(float(x), 3) for x in kern_dev],
                        "samples": dev_samples,
                        "frame_ms_root": round(float(np.mean(frame_ms)), 3),
@@ -700,13 +760,16 @@ def main(argv=None):
             events[2].record(stream)
         return out
 
-    # S_bar from the kernel's own segment counter (untimed)
-    step(count=True)
-    torch.cuda.synchronize()
-    seg_local, sph_local, box_local = (int(v) for v in segs.cpu().tolist())
-    if args.reference_f64:  # the reference's linear scan: every sphere per segment (ref64.hpp counts segments only)
-        sph_local = seg_local * ctx.n_spheres
-    for _ in range(max(0, args.warmup - 1)):
+    full = args.full
+    warm = args.warmup
+    if full:  # S_bar from the kernel's own segment counter (untimed: the first warm-up frame)
+        step(count=True)
+        torch.cuda.synchronize()
+        seg_local, sph_local, box_local = (int(v) for v in segs.cpu().tolist())
+        if args.reference_f64:  # the reference's linear scan: every sphere per segment (ref64.hpp counts segments only)
+            sph_local = seg_local * ctx.n_spheres
+        warm -= 1
+    for _ in range(max(0, warm)):
         step()
     torch.cuda.synchronize()
 
@@ -715,44 +778,47 @@ def main(argv=None):
     # render + un-shard (the one-slab "gather" is the identity), plus its
     # kernel's HIP events
     t1_frame = None
-    if world > 1 and args.t1 == "auto":
+    if full and world > 1 and args.t1 == "auto":
         if rank == 0:
             p1 = ptgpu.make_params(W, H, samps, nsub, ptgpu.DEFAULT_SEED, args.band_rows, 0, 1, args.chunk, flags=f64)
-            full = torch.empty(ptgpu.shard_rows(H, args.band_rows, 1) * W * 3, dtype=torch.float32, device=dev)
+            whole = torch.empty(ptgpu.shard_rows(H, args.band_rows, 1) * W * 3, dtype=torch.float32, device=dev)
             img1 = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-            ctx.render_device(full, p1, None, stream)  # warm-up (allocates the accumulator)
+            ctx.render_device(whole, p1, None, stream)  # warm-up (allocates the accumulator)
             torch.cuda.synchronize()
             k1 = max(1, args.t1_steps)
             ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(k1)]
             w0 = time.perf_counter()
             for e0, e1 in ev:
                 e0.record(stream)
-                ctx.render_device(full, p1, None, stream)
+                ctx.render_device(whole, p1, None, stream)
                 e1.record(stream)
-                ptgpu.unshard_device(full, img1, W, H, args.band_rows, 1, stream)
+                ptgpu.unshard_device(whole, img1, W, H, args.band_rows, 1, stream)
                 torch.cuda.synchronize()
             t1_frame = {"wall_ms": round((time.perf_counter() - w0) / k1 * 1e3, 3),
                         "kernel_ms": round(float(np.mean([a.elapsed_time(b) for a, b in ev])), 3), "frames": k1}
-            del full, img1
+            del whole, img1
         dist.barrier()
 
-    evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(args.steps)]
+    # HIP events around the render and the gather of every timed step (--full)
+    evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) if full else None
+           for _ in range(args.steps)]
+    last = None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(events=evs[i])
+        last = step(events=evs[i])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b, _ in evs])) if args.steps else float("nan")
-    gather_ms = float(np.mean([b.elapsed_time(c) for _, b, c in evs])) if args.steps else float("nan")
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b, _ in evs])) if full and args.steps else float("nan")
+    gather_ms = float(np.mean([b.elapsed_time(c) for _, b, c in evs])) if full and args.steps else float("nan")
     per_rank = None
     kern_max = kern_ms
-    if world > 1:  # per-rank render and gather (+ un-shard on rank 0) times, HIP events on the launch stream
+    if full and world > 1:  # per-rank render and gather (+ un-shard on rank 0) times, HIP events on the launch stream
         cdev0 = torch.device("cpu") if rehearsal else dev
         mine = torch.tensor([kern_ms, gather_ms], dtype=torch.float64, device=cdev0)
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -762,36 +828,43 @@ def main(argv=None):
                     "note": "gather_ms: the RCCL gather (and rank 0's un-shard), incl. waiting for the slowest rank"}
         kern_max = max(float(t[0]) for t in allr)
 
-    seg_total = seg_local
     if world > 1:
         cdev = torch.device("cpu") if rehearsal else dev
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+    seg_total = seg_local if full else None
+    if full and world > 1:
         s = torch.tensor([seg_local, sph_local, box_local], dtype=torch.int64, device=cdev)
         dist.all_reduce(s)
         seg_total, sph_local, box_local = (int(v) for v in s.cpu().tolist())
 
     if rank == 0:
-        frame_samples = W * H * spp
-        pmc = load_pmc(f"{scene} {W}x{H} {spp}spp")
-        s_bar, roof = roofline(frame_samples, seg_total, sph_local, box_local, my_rows * W * spp, kern_ms,
-                               ctx.n_spheres, pmc)
         par = ((f"tile-sharded row bands x{world}, one process per GPU (torch.distributed nccl = RCCL)"
                 + (" (gloo rehearsal on one GPU)" if rehearsal else "")) if world > 1 else "single GPU")
         value, out = base_line(args, world, wl_name, scene, W, H, spp, samps, nsub, ctx.n_spheres, elapsed, par)
-        out["segments_per_s"] = round(value * 1e6 * s_bar, 1)
-        out["roofline"] = roof
-        out["roofline"]["scan_kernel"] = scan_kernel_name(ctx.launch_info(params))
         cpu = None
-        if world == 1 and args.cpu_baseline == "auto":
-            frame = slab.cpu().numpy().reshape(rows, W, 3)[:H]  # band_rows = 1, one shard: slab row = image row
-            cpu = cpu_baseline(scene, W, H, samps, nsub, args.cpu_threads or default_cpu_threads(),
-                               max(1, args.cpu_row_step), frame, ptgpu.DEFAULT_SEED, args.quality_rows)
-        out["cpu_baseline"] = cpu
+        if full:
+            frame_samples = W * H * spp
+            pmc = load_pmc(f"{scene} {W}x{H} {spp}spp")
+            s_bar, roof = roofline(frame_samples, seg_total, sph_local, box_local, my_rows * W * spp, kern_ms,
+                                   ctx.n_spheres, pmc)
+            out["segments_per_s"] = round(value * 1e6 * s_bar, 1)
+            out["roofline"] = roof
+            out["roofline"]["scan_kernel"] = scan_kernel_name(ctx.launch_info(params))
+            if world == 1 and args.cpu_baseline == "auto":
+                frame = slab.cpu().numpy().reshape(rows, W, 3)[:H]  # band_rows = 1, one shard: slab row = image row
+                cpu = cpu_baseline(scene, W, H, samps, nsub, args.cpu_threads or default_cpu_threads(),
+                                   max(1, args.cpu_row_step), frame, ptgpu.DEFAULT_SEED, args.quality_rows)
+            out["cpu_baseline"] = cpu
         out["launch"] = "torchrun" if world > 1 else "single"
         if group is not None:
             out.update(group)
+        if args.dump_outputs and last is not None:
+            # the last timed step's frame: rank 0's un-sharded image at N > 1, else the one slab in image rows
+            image = last.cpu().numpy() if world > 1 else \
+                ptgpu.unshard_host(last.cpu().numpy(), W, H, args.band_rows, 1)
+            out["outputs"] = dump_outputs(args.dump_outputs, image)
         if per_rank is not None:
             out["per_rank"] = per_rank
         if t1_frame is not None:

@@ -14,7 +14,7 @@ shift || true
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 out=gpurun_out/prof_${tag}
 mkdir -p "$out"
-BENCH=(bench.py --steps 2 --warmup 1 --cpu-baseline off "$@")
+BENCH=(bench.py --full --steps 2 --warmup 1 --cpu-baseline off "$@")
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/trace" -o run --output-format csv -- python3 "${BENCH[@]}" > "$out/bench_trace.json" 2> "$out/trace.err"
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$out/fetch" -o run --output-format csv -- python3 "${BENCH[@]}" > "$out/bench_fetch.json" 2> "$out/fetch.err"
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d "$out/write" -o run --output-format csv -- python3 "${BENCH[@]}" > "$out/bench_write.json" 2> "$out/write.err"

@@ -104,6 +104,43 @@ def test_launch_inprocess_flag():
     assert bench.parse_args([]).launch == "auto"
 
 
+def test_full_and_dump_outputs_flags():
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d" and (a.steps, a.warmup) == (7, 2)
+
+
+def test_dump_outputs_whole_frame(tmp_path):
+    img = bench.np.arange(5 * 4 * 3, dtype=bench.np.float64).reshape(5, 4, 3)
+    info = bench.dump_outputs(str(tmp_path / "a" / "b"), img)
+    got = bench.np.load(tmp_path / "a" / "b" / "image.npy")
+    assert got.dtype == bench.np.float32 and bench.np.array_equal(got, img)
+    assert info["image"]["shape"] == [5, 4, 3] and info["image"]["rows"] == "all"
+    assert sorted(os.listdir(tmp_path / "a" / "b")) == ["image.npy"]
+
+
+def test_dump_outputs_samples_rows_of_a_large_frame(tmp_path, monkeypatch):
+    """Over the size limit: a sample of whole rows, the same rows every time,
+    their indices beside the image; both files together stay under the limit."""
+    np = bench.np
+    img = np.random.default_rng(1).random((64, 8, 3), dtype=np.float32)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (8 * 3 * 4 + 8))
+    bench.dump_outputs(str(tmp_path / "x"), img)
+    bench.dump_outputs(str(tmp_path / "y"), img)
+    rows = np.load(tmp_path / "x" / "image_rows.npy")
+    got = np.load(tmp_path / "x" / "image.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and len(set(rows.tolist())) == 10
+    assert (np.diff(rows) > 0).all() and rows.min() >= 0 and rows.max() < 64
+    assert got.dtype == np.float32 and np.array_equal(got, img[rows.astype(int)])
+    assert got.nbytes + rows.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(rows, np.load(tmp_path / "y" / "image_rows.npy"))
+    assert np.array_equal(got, np.load(tmp_path / "y" / "image.npy"))
+    # the real limit leaves the metric's frame whole and keeps C4's under 64 MB
+    monkeypatch.undo()
+    assert 1920 * 1080 * 3 * 4 <= bench.DUMP_LIMIT_BYTES < 64 * 10**6 - 4096
+
+
 def test_roofline_fields():
     pmc = {"valu_fp32_share": 0.49, "hbm_bytes_per_launch": 1, "tag": "x"}
     s_bar, r = bench.roofline(100, 1200, 8 * 1200, 0, 100, 1e-6, 8, pmc)

@@ -14,7 +14,7 @@ for r in $(seq 1 $rounds); do
       lib=cpu-path-tracing_amd/build/libptgpu_$v.so; [ $v = main ] && lib=cpu-path-tracing_amd/libptgpu.so
       name=$(echo "$tok" | tr -c 'A-Za-z0-9_\n' '_')
       out=gpurun_out/ab_${tag}_$name.json
-      PTGPU_LIB=$lib timeout -k 10 150 python bench.py --cpu-baseline off $w $extra > $out 2>/dev/null || { echo "$tok [$w] failed"; exit 1; }
+      PTGPU_LIB=$lib timeout -k 10 150 python bench.py --full --cpu-baseline off $w $extra > $out 2>/dev/null || { echo "$tok [$w] failed"; exit 1; }
       python -c "import json;d=json.load(open('$out'));r=d['roofline'];print('$tok', d['config']['workload'], 'round $r', d['ms_per_step'], r['kernel_ms'], r['frac'], 'box/seg', r.get('box_tests_per_segment', r.get('wall_tests_per_segment_executed')), 'sph/seg', r.get('sphere_tests_per_segment_executed'), r.get('scan_kernel'))"
     done
   done
