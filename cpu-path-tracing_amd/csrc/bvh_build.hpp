@@ -268,7 +268,7 @@ inline int bvh_octant_mask(const BvhBuild &b)
     return mask;
 }
 
-// huge[i]: sphere i takes the anchored form (ptg_render.hip is_huge) and is
+// huge[i]: sphere i takes the anchored form (kernel_args.hpp is_huge) and is
 // tested linearly, outside the tree
 inline BvhBuild build_bvh(const ptg_sphere *s, int n, const std::vector<char> &huge)
 {

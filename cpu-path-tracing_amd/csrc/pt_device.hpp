@@ -219,7 +219,7 @@ inline void trig_table(float *tab /* 2 * kTrigEntries */)
     }
 }
 
-// Scene records prepared on the host (ptg_render.hip: prepare_scene).
+// Scene records prepared on the host (scene_prep.hpp: prepare_scene).
 // Geometry, 32 B per sphere, read with wave-uniform (scalar) loads:
 //   g0 = {P.x, P.y, P.z, k1}, g1 = {N.x, N.y, N.z, k2}
 //   huge sphere (R >= 1000): P = C + R*n0 on the surface facing the camera,

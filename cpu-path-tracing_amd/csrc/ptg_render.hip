@@ -29,20 +29,16 @@
 
 #include "../../include/ptgpu.h"
 #include "bvh_build.hpp"
+#include "kernel_args.hpp"  // KArgs and the constants shared with the host side
+#include "launch_plan.hpp"  // check_params, fill_launch and their tunables
 #include "pt_device.hpp"
+#include "ptg_error.hpp"
 #include "ref64.hpp"
+#include "scene_prep.hpp"  // scene records, scan order, box mode, the uploads
 
 using namespace ptg;
 
 namespace {
-
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string &msg)
-{
-    g_last_error = msg;
-    return code;
-}
 
 #define PTG_HIP(call)                                                                              \
     do {                                                                                           \
@@ -50,25 +46,7 @@ int fail(int code, const std::string &msg)
         if (e_ != hipSuccess)                                                                      \
             return fail(PTG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));           \
     } while (0)
-// inside ptg_context_create, once `ctx` exists: release it on failure
-#define PTG_HIP_OR_DESTROY(call)                                                                   \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            ptg_context_destroy(ctx);                                                              \
-            return fail(PTG_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));           \
-        }                                                                                          \
-    } while (0)
 
-#ifndef PTG_BLOCK
-#define PTG_BLOCK 256  // linear-scene render kernel workgroup size
-#endif
-constexpr int kBlock = PTG_BLOCK;
-constexpr int kMaxLevels = 4;     // unit levels: head + up to 3 split-tail levels
-// samples per sub-pixel in one work unit, at most: a unit's paths are indexed
-// it < 64 * chunk <= 2^22, where render_kernel's float-reciprocal divmod_nv is
-// exact (fill_launch caps every level's chunk)
-constexpr int kMaxChunk = 1 << 16;
 constexpr int kTraceBlock = 256;  // parity probe kernel
 #ifndef PTG_MAX_LDS_SPHERES
 #define PTG_MAX_LDS_SPHERES 64
@@ -78,13 +56,6 @@ constexpr int kTraceBlock = 256;  // parity probe kernel
 // workgroups fit a CU (measured: shading in LDS +1.3 % over geometry-only
 // staging, which itself beat scalar loads by 1.5 %)
 constexpr int kMaxLdsSpheres = PTG_MAX_LDS_SPHERES;
-// nearest-hit rule and scan: <= kLinearMax spheres -> linear scan from LDS with
-// fraction comparisons; more -> BVH with the reference's per-candidate
-// division rule (DESIGN.md "scene scan"); the oracle switches at the same n
-#ifndef PTG_LINEAR_MAX
-#define PTG_LINEAR_MAX 64
-#endif
-constexpr int kLinearMax = PTG_LINEAR_MAX;
 static_assert(kLinearMax <= kMaxLdsSpheres, "linear scenes must fit in LDS");
 #ifndef PTG_REFILL_BATCH
 #define PTG_REFILL_BATCH 40  // measured: 40 beats 32 by 0.35 % (box) / 0.6 % (box_mirror), ties 48-56; 24 is 1.2 % slower
@@ -98,57 +69,8 @@ static_assert(kLinearMax <= kMaxLdsSpheres, "linear scenes must fit in LDS");
 #ifndef PTG_LONG_LEAF
 #define PTG_LONG_LEAF 5  // BVH leaf phase: leaves of at least this many spheres get helpers first (and a second one; 5 beats 4 by 0.9 %, 3 and 6 worse)
 #endif
-#ifndef PTG_BVH_UNIT_MULT
-#define PTG_BVH_UNIT_MULT 2  // BVH scenes below the split-tail threshold: this many times more work units (8-way C5 shards: 2 beats 1 and 4 by 2-5 %)
-#endif
-#ifndef PTG_TAIL_CHUNKS
-#define PTG_TAIL_CHUNKS 8  // split-tail units per pixel group of the last rows (1: off)
-#endif
-#ifndef PTG_TAIL_LEVELS
-// split-tail levels, each with twice the chunks of the one before (<= 3);
-// measured: 2 or 3 levels (chunks 4/8/16) within 1 % of 1 level on the bench
-// frame, its 2-8-way shards and box 1024x768
-#define PTG_TAIL_LEVELS 1
-#endif
-#ifndef PTG_TAIL_CHUNKS_MANY
-// ... with at least 5 rounds of wave slots (measured: box 1024x768x256 spp
-// 2 % faster with 4 than with 8, the 1920x1080 frame the same; 2-8-way shards
-// of that frame, 2-4 rounds, keep 8)
-#define PTG_TAIL_CHUNKS_MANY 4
-#endif
-#ifndef PTG_BVH_TAIL_CHUNKS_MANY
-// ... and for BVH scenes, whose pixel-split tail units carry every sample of
-// their pixels (no HBM accumulation either way): 8 units of 2 pixels per
-// group (C5 -0.85 % against 4, A/B 244.4-244.7 vs 246.3-247.1 ms; the box
-// scenes keep 4, the cooperative LDS-reduced level)
-#define PTG_BVH_TAIL_CHUNKS_MANY 8
-#endif
-#ifndef PTG_LIN_TAIL_HALF_ROUNDS
-#define PTG_LIN_TAIL_HALF_ROUNDS 2  // linear scenes: split-tail rows, in half rounds of the device's wave slots
-#endif
-#ifndef PTG_BVH_TAIL_HALF_ROUNDS
-#define PTG_BVH_TAIL_HALF_ROUNDS 2  // BVH scenes: split-tail rows, in half rounds of the device's wave slots
-#endif
-#ifndef PTG_TAIL_MIN_HALF_ROUNDS
-// linear scenes: split tail from 1.5 rounds of wave slots on (measured with
-// tools/shard_sim.py: 2/4/8-way shards of the bench frame 1.6/1.8/1.4 %
-// faster than with their samples split into ~96k units)
-#define PTG_TAIL_MIN_HALF_ROUNDS 3
-#endif
 #ifndef PTG_BVH_STACK
 #define PTG_BVH_STACK 3  // wide walk: per-lane stack entries before the continuation fallback (3: C5 -0.7 % vs 2, A/B 258.3 vs 260.1 ms)
-#endif
-#ifndef PTG_BVH_TAIL_MIN_HALF_ROUNDS
-#define PTG_BVH_TAIL_MIN_HALF_ROUNDS 6  // BVH scenes: split tail from 3 rounds of wave slots on
-#endif
-#ifndef PTG_BVH_HEAD_CHUNK
-#define PTG_BVH_HEAD_CHUNK 128  // BVH scenes below the split-tail threshold: head rows in chunks of this many samples (0: off; C5 8-way shard 50.4 -> 48.1 ms; 64/96 within 0.5 %, whole pixels +45 %)
-#endif
-#ifndef PTG_BVH_HEAD_TAIL_HALF_ROUNDS
-#define PTG_BVH_HEAD_TAIL_HALF_ROUNDS 1  // ... and the last rows, this many half rounds of wave slots, in the auto chunk (1 beats 2 by 2.5 %, 3 by 5 %)
-#endif
-#ifndef PTG_BVH_TAIL_CHUNK
-#define PTG_BVH_TAIL_CHUNK 0  // ... in chunks of this many samples (0: the auto chunk, 20 at C5 8-way; 10: +0.8 %, 32: +5 %)
 #endif
 #ifndef PTG_READY_FRAC
 #define PTG_READY_FRAC 6  // BVH: stop walking and shade once 6/8 of the active lanes have finished their scan
@@ -220,117 +142,8 @@ __device__ unsigned long long ptg_unit_trace[3 * kTraceUnits];
 #ifndef PTG_MIN_WAVES_PER_EU
 #define PTG_MIN_WAVES_PER_EU 8  // 8 waves per SIMD: <= 64 VGPRs and <= 80 SGPRs (8 blocks of 256 per CU)
 #endif
-#ifndef PTG_BVH_BLOCK
-#define PTG_BVH_BLOCK 64  // BVH render kernel: one wave per workgroup, so a wave slot frees as soon as its unit ends
-                          // (units of the 10,000-sphere scene differ widely in length: 64 beats 256 by 10 %, 128 by 6 %)
-#endif
 template <bool kBvh>
 constexpr int kBlockOf = kBvh ? PTG_BVH_BLOCK : kBlock;
-constexpr double kBigRadius = 1000.0;
-// A sphere takes the anchored form ("huge", DESIGN.md "huge spheres") when its
-// radius is >= 1000 or more than 16 times the camera's distance to its
-// surface (+1): locally plane-like for the scene, where c = |o - C|^2 - R^2
-// cancels in fp32 (simple_scene's R = 100 ground: RMSE vs fp64 1.5e-3 ->
-// 3.3e-4).  The oracle's is_huge_B applies the same rule.
-inline bool is_huge(const ptg_sphere &sp, const ptg_camera *cam)
-{
-    if (sp.radius >= kBigRadius)
-        return true;
-    double d2 = 0.0;
-    for (int c = 0; c < 3; ++c)
-        d2 += (cam->position[c] - sp.position[c]) * (cam->position[c] - sp.position[c]);
-    return sp.radius > 16.0 * (std::fabs(std::sqrt(d2) - sp.radius) + 1.0);
-}
-
-struct KArgs {
-    const LinRec *lin;      // linear scenes (<= kLinearMax): n records in scan order + sentinel
-    const ShadeRec *shade;  // BVH scenes: shading records in scene index order
-    int n;
-    // linear scenes: records in SCAN order (prepare_scan_order), grouped by
-    // kind: [0, end_ax[0]) huge spheres anchored on the x axis, then y, then z
-    // ([end_ax[k-1], end_ax[k])), then general huge spheres up to end_big,
-    // then the small spheres up to n
-    int end_ax[3];
-    int end_big;
-    int box_walls_out;  // box mode's walls: no ray starts inside any (outside_only); else the fast mode scans generically
-    // wall pairs (pair_walls): axis k's group starts with a pair when
-    // pairs[k] = 1 -- its wall on the + side, then its wall on the - side; a
-    // lane whose origin lies in [pair_lo[k], pair_hi[k]] tests only the wall
-    // its direction moves toward (d_k >= 0: the + wall)
-    int pairs[3];
-    float pair_lo[3], pair_hi[3];
-    // box mode (scan_order_of: every axis-anchored wall belongs to the one
-    // pair or is the one single wall of its axis, at least one pair, no
-    // other huge sphere): per axis the + and - walls' records (-1: none) and
-    // tangent planes (+-inf: none); pair_lo/hi bound the room on every
-    // axis (+-kFarPlane where open)
-    int box_mode;
-    int rec_plus[3], rec_minus[3];  // byte offsets of the records
-    float plane_plus[3], plane_minus[3];
-    // box mode: -m, m > 0 the smallest gap between a wall's tangent plane and
-    // its room bound (pair_lo/hi) less a rounding margin: an origin whose
-    // plane distances up/um (scene_scan) are all >= -m lies inside the room
-    // bounds (room_neg_margin); +inf where there is no such gap
-    float room_nmr;
-    // scenes with more than kLinearMax spheres: BVH (bvh_build.hpp)
-    // the 4-wide tree (bvh_build.hpp wide_bvh): 8 near-plane-first layouts,
-    // one per ray-direction octant, interleaved node by node (node j of
-    // layout k at node 8 j + k), 4 records of 16 B per node
-    const uint4 *bvh_qnodes;
-    float q_lo[3], q_scale[3];  // box grid: plane = q_lo + value * q_scale (binary16 values)
-    const float4 *bvh_sph;    // leaf-ordered spheres {C, -R^2} (BVH leaves hold only non-huge spheres)
-    const int *bvh_id;        // leaf-ordered scene indices
-    const GeoRec *big_geo;    // huge spheres, tested linearly
-    const int *big_id;
-    int n_nodes, n_big;
-    const int *bvh_cont;  // per wide node (first record / 4) its continuation (bvh_build.hpp wide_conts)
-    const float2 *trig;  // {cos, sin}(2 pi k / 128), staged in LDS (sincos2pi_tab)
-    // camera (camera.cpp:32-38): pos, base = llc - pos, X, Y, lens_radius
-    float pos_x, pos_y, pos_z;
-    float base_x, base_y, base_z;
-    float X_x, X_y, X_z;
-    float Y_x, Y_y, Y_z;
-    float lens;
-    // image / sampling
-    int W, H, samps, nsub, lanes_per_pixel, pixels_per_wave, waves_per_row;
-    int slab_rows, band_rows, shard_rank, shard_count;
-    float invW, invH, inv_samps, sub_len, inv_sub2;
-    unsigned long long seed;
-    int chunk, n_groups, single_chunk;
-    // unit levels (fill_launch): level l covers pixel groups [lvl_group[l],
-    // lvl_group[l + 1]) in chunks of lvl_chunk[l] samples, chunk-major, as
-    // units [lvl_unit[l], lvl_unit[l + 1]); level 0 is the head, levels >= 1
-    // the split tail (accumulated, then resolve_kernel from slab row
-    // resolve_row0).  lvl_group[n_levels] = n_groups.
-    int n_levels;
-    int lvl_group[kMaxLevels + 1], lvl_chunk[kMaxLevels];
-    // cooperative level (linear kernel's split tail with as many chunks as a
-    // workgroup has waves): the waves of one workgroup take the chunks of one
-    // pixel group, the last wave to finish adds the others' LDS sums and
-    // resolves -- no HBM accumulator (lvl_unit[l] is a multiple of the
-    // waves per workgroup)
-    int lvl_coop[kMaxLevels];
-    // pixel-split level (the BVH kernel's split tail): each pixel group in
-    // lvl_psplit[l] units, unit k taking the group's pixels k, k + ps, k + 2ps,
-    // ... (interleaved, so the units of a group cost about the same) with
-    // every sample (lvl_inwave: resolved in the wave, nothing accumulated in
-    // HBM); 1 elsewhere
-    int lvl_psplit[kMaxLevels];
-    int lvl_inwave[kMaxLevels];  // the level's units hold every sample of their pixels
-    int needs_resolve;  // some level accumulates in HBM: resolve_kernel from resolve_row0
-    long long lvl_unit[kMaxLevels + 1];
-    int resolve_row0;
-    int sample_begin, sample_end;  // samples [begin, end) of every sub-pixel in this launch
-    int keep_acc;                  // resolve without re-zeroing (progressive previews)
-    int count_tests;               // PTG_FLAG_COUNT_TESTS: segments[1..2] += sphere tests, box tests
-    int count_nonfinite;           // PTG_FLAG_COUNT_NONFINITE: segments[3] += paths quant() would clip
-    int exact_math;                // PTG_FLAG_EXACT_MATH: the kernels' exact arithmetic (pt_device.hpp Math)
-    long long n_units;
-    float *out;
-    unsigned long long *acc;  // slab_rows * W * lanes_per_pixel * 3 exact sums
-    unsigned long long *segments;
-};
-
 struct Lane {
     int x, y, sx, sy;
     uint64_t key;
@@ -394,17 +207,9 @@ __device__ __forceinline__ void camera_ray(const CamC &C, const Lane &L, uint32_
 // DESIGN.md "scene scan") are exact early-outs that never let a wave skip the
 // sqrt in practice, so they are left out here (-15 % frame time, same bits).
 constexpr float kCullMargin = 0x1.00001p+0f;  // 1 + 2^-20 (BVH leaf test)
-constexpr float kFarPlane = 1e30f;             // box mode: the room bound of an open side
 constexpr float kPlaneMargin = 0x1.ffep-1f;    // 1 - 2^-12: box mode's wall skip test
 
 enum : int { kAxX = 0, kAxY = 1, kAxZ = 2, kBig = 3, kSmall = 4, kAxAny = 5, kAxSel = 6, kAxAnyOut = 7 };
-
-#ifndef PTG_UNIT_ROUNDS
-#define PTG_UNIT_ROUNDS 2  // linear scenes below the split-tail size: work units for this many rounds of wave slots (2 beats 4 by 5 %, 12 by 12 % on C1)
-#endif
-
-
-
 
 __device__ __forceinline__ float comp(f3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
 
@@ -1447,7 +1252,7 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
 }
 
 // Slab row -> image (output) row for the band shard.
-__device__ __forceinline__ int out_row_of(const KArgs &A, int slab_row)
+__host__ __device__ __forceinline__ int out_row_of(const KArgs &A, int slab_row)
 {
     int band = slab_row / A.band_rows;
     return (band * A.shard_count + A.shard_rank) * A.band_rows + (slab_row - band * A.band_rows);
@@ -2192,557 +1997,6 @@ struct ptg_context {
 
 namespace {
 
-bool sphere_ok(const ptg_sphere &s)
-{
-    if (!(s.radius > 0.0) || !std::isfinite(s.radius))
-        return false;
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(s.position[c]) || !std::isfinite(s.emission[c]) || !std::isfinite(s.color[c]))
-            return false;
-    return s.material >= PTG_DIFFUSE && s.material <= PTG_DIELECTRIC;
-}
-
-// Anchor of a huge sphere (DESIGN.md "Huge spheres"): the point P = C + R n0
-// of the sphere and its outward normal n0.  The default n0 is the unit vector
-// from C towards the camera.  When the point C + s R e_k of the dominant axis
-// direction of that n0 (k = largest |n0_k|, s = its sign) lies near the scene
-// -- within max(diagonal, 1) of the box around the camera and the non-huge
-// spheres -- that axis point is the anchor instead: any point of the sphere is
-// an exact anchor, and one near the scene keeps |o - P| at scene scale (box
-// walls: the axis points lie inside that box).  Returns k, or -1 for the
-// camera-facing anchor.  The oracle's prep_B makes the same choice
-// (oracle/pt_oracle.c: choose_anchor_B).
-struct SceneBox {
-    double lo[3], hi[3], diag;
-};
-
-int choose_anchor(const ptg_sphere &sp, const ptg_camera *cam, const SceneBox &box, double P[3], double N[3])
-{
-    const double R = sp.radius;
-    double v[3], len2 = 0.0;
-    for (int c = 0; c < 3; ++c) {
-        v[c] = cam->position[c] - sp.position[c];
-        len2 += v[c] * v[c];
-    }
-    const double len = std::sqrt(len2);
-    for (int c = 0; c < 3; ++c)
-        N[c] = len > 0.0 ? v[c] / len : (c == 1 ? 1.0 : 0.0);
-    int k = 0;
-    for (int c = 1; c < 3; ++c)
-        if (std::fabs(N[c]) > std::fabs(N[k]))
-            k = c;
-    const double s = N[k] >= 0.0 ? 1.0 : -1.0;
-    double out2 = 0.0;  // squared distance of the axis point from the scene box
-    for (int c = 0; c < 3; ++c) {
-        const double pa = sp.position[c] + (c == k ? s * R : 0.0);
-        const double o = pa < box.lo[c] ? box.lo[c] - pa : (pa > box.hi[c] ? pa - box.hi[c] : 0.0);
-        out2 += o * o;
-    }
-    const bool snap = std::sqrt(out2) <= std::max(box.diag, 1.0);
-    for (int c = 0; c < 3; ++c) {
-        if (snap)
-            N[c] = c == k ? s : 0.0;
-        P[c] = sp.position[c] + R * N[c];
-    }
-    return snap ? k : -1;
-}
-
-// Box around the camera and every non-huge sphere, and its diagonal.
-SceneBox scene_box(const ptg_sphere *s, int n, const ptg_camera *cam)
-{
-    SceneBox b;
-    for (int c = 0; c < 3; ++c)
-        b.lo[c] = b.hi[c] = cam->position[c];
-    for (int i = 0; i < n; ++i) {
-        if (is_huge(s[i], cam))
-            continue;
-        for (int c = 0; c < 3; ++c) {
-            b.lo[c] = std::min(b.lo[c], s[i].position[c] - s[i].radius);
-            b.hi[c] = std::max(b.hi[c], s[i].position[c] + s[i].radius);
-        }
-    }
-    double d2 = 0.0;
-    for (int c = 0; c < 3; ++c)
-        d2 += (b.hi[c] - b.lo[c]) * (b.hi[c] - b.lo[c]);
-    b.diag = std::sqrt(d2);
-    return b;
-}
-
-// Host-side preparation (double -> fp32 records, scene index order), the
-// counterpart of the oracle's Mode B prep_B.  axis[i] = anchor axis of a huge
-// sphere (-1: camera-facing anchor or not huge).
-void prepare_scene(const ptg_sphere *s, int n, const ptg_camera *cam, std::vector<GeoRec> &geo,
-                   std::vector<ShadeRec> &shade, std::vector<int> &axis)
-{
-    geo.resize(n);
-    shade.resize(n);
-    axis.assign(n, -1);
-    const SceneBox box = scene_box(s, n, cam);
-    for (int i = 0; i < n; ++i) {
-        const ptg_sphere &sp = s[i];
-        const double R = sp.radius;
-        GeoRec g;
-        if (is_huge(sp, cam)) {
-            double P[3], N[3];
-            axis[i] = choose_anchor(sp, cam, box, P, N);
-            g.g0 = make_float4((float)P[0], (float)P[1], (float)P[2], (float)R);
-            g.g1 = make_float4((float)N[0], (float)N[1], (float)N[2], (float)(2.0 * R));
-        } else {
-            g.g0 = make_float4((float)sp.position[0], (float)sp.position[1], (float)sp.position[2],
-                               (float)(-(R * R)));
-            g.g1 = make_float4(0.0f, 0.0f, 0.0f, (float)(-(R * R)));
-        }
-        geo[i] = g;
-        ShadeRec r;
-        float cx = (float)sp.color[0], cy = (float)sp.color[1], cz = (float)sp.color[2];
-        float p = cx;
-        if (p < cy) p = cy;
-        if (p < cz) p = cz;
-        float rx = 0.0f, ry = 0.0f, rz = 0.0f;
-        if (p > 0.0f) {
-            float inv = 1.0f / p;
-            rx = cx * inv;
-            ry = cy * inv;
-            rz = cz * inv;
-        }
-        int32_t mat = sp.material;
-        float matf;
-        std::memcpy(&matf, &mat, 4);
-        // Russian roulette as an integer compare (main.cpp:130-131, u < p):
-        // u = m 2^-24 exactly (m the draw's 24-bit integer), so u < p <=> m <
-        // p 2^24 <=> m < ceil(p 2^24) -- the same decisions as the oracle's
-        // float compare, without the draw's convert and scale
-        uint32_t p24 = !(p > 0.0f) ? 0u : (p >= 1.0f ? (1u << 24) : (uint32_t)std::ceil((double)p * 16777216.0));
-        float p24f;
-        std::memcpy(&p24f, &p24, 4);
-        r.s0 = make_float4((float)sp.position[0], (float)sp.position[1], (float)sp.position[2], p24f);
-        r.s1 = make_float4((float)sp.emission[0], (float)sp.emission[1], (float)sp.emission[2], matf);
-        r.s2 = make_float4(cx, cy, cz, (float)(1.0 / R));
-        r.s3 = make_float4(rx, ry, rz, (float)(1.0 / R));
-        shade[i] = r;
-    }
-}
-
-// Wall pairs (DESIGN.md "wall pairs"): on each axis k, the first (scene
-// index order) axis-anchored huge sphere whose centre lies on the + side of
-// its anchor (anchor normal -e_k) and the first one on the - side.  Their
-// tangent planes at the anchors, x_k = a_plus and x_k = a_minus, bound the
-// room: a ray from an origin with a_minus <= o_k <= a_plus can hit the + wall
-// only if d_k > 0 and the - wall only if d_k < 0 (each sphere lies entirely
-// beyond its tangent plane).  The bounds widen by a margin of 1e-4 max(1, box
-// diagonal) so that rays leaving a wall (origin rounded a hair past its
-// plane) keep the rule; pair_lo/hi are those bounds rounded to float.  The
-// oracle's prep_B forms the same pairs (pt_oracle.c).  plus[k] / minus[k] =
-// scene index or -1.
-// A wall may take part in wall pairs / box mode only if no ray origin can lie
-// genuinely inside it, beyond its tangent plane, where the "test only the
-// wall the ray moves toward" rule would drop a hit of the wall from inside:
-// the wall is not dielectric (no path is transmitted into it) and the camera
-// is on the room side by more than the margin.  Other spheres need no check:
-// a sphere sunk into the wall has its sunk part inside the wall, which a ray
-// from the room reaches only through the wall's surface -- the wall is hit
-// there first (tests/test_scene_file.py: a glass sphere sunk into a wall,
-// pairs on vs every sphere tested, same image).  The oracle's wall_clear_B
-// makes the same choice.
-bool wall_clear(const ptg_sphere *s, int i, int k, bool plus_side, const ptg_camera *cam, const SceneBox &box)
-{
-    if (s[i].material == PTG_DIELECTRIC)
-        return false;
-    const double margin = 1e-4 * std::max(1.0, box.diag);
-    const double a = plus_side ? s[i].position[k] - s[i].radius : s[i].position[k] + s[i].radius;
-    return plus_side ? cam->position[k] < a - margin : cam->position[k] > a + margin;
-}
-
-void pair_walls(const ptg_sphere *s, int n, const std::vector<int> &axis, const std::vector<GeoRec> &geo,
-                const ptg_camera *cam, const SceneBox &box, int plus[3], int minus[3], float lo[3], float hi[3])
-{
-    const double margin = 1e-4 * std::max(1.0, box.diag);
-    for (int k = 0; k < 3; ++k) {
-        plus[k] = minus[k] = -1;
-        for (int i = 0; i < n; ++i) {
-            if (axis[i] != k)
-                continue;
-            const float nk = (&geo[i].g1.x)[k];  // anchor normal component: exactly +-1
-            if (nk < 0.0f && plus[k] < 0)
-                plus[k] = i;
-            if (nk > 0.0f && minus[k] < 0)
-                minus[k] = i;
-        }
-        if (plus[k] < 0 || minus[k] < 0 || !wall_clear(s, plus[k], k, true, cam, box) ||
-            !wall_clear(s, minus[k], k, false, cam, box)) {
-            plus[k] = minus[k] = -1;
-            lo[k] = hi[k] = 0.0f;
-            continue;
-        }
-        const double a_plus = s[plus[k]].position[k] - s[plus[k]].radius;
-        const double a_minus = s[minus[k]].position[k] + s[minus[k]].radius;
-        lo[k] = (float)(a_minus - margin);
-        hi[k] = (float)(a_plus + margin);
-    }
-}
-
-// Box mode (scene_scan; DESIGN.md "box mode"): on when every axis-anchored
-// wall is either one of its axis's pair or the only wall of its axis, at
-// least one axis has a pair, and there is no other huge sphere.  Fills the
-// per-axis records (scan positions in `order`) and tangent planes (the
-// records' anchor coordinate), and extends the pair bounds to single walls
-// (margin as pair_walls) and open sides (+-kFarPlane).  The oracle's prep_B
-// makes the same choice.
-// A sphere no ray can start inside (KArgs::box_walls_out).  A camera ray starts
-// outside every sphere whose centre is farther from the camera than its
-// radius plus the lens offset (< 2 lens radii: camera_ray's rd * (s + t));
-// a ray reaches a surface point
-// only from outside every opaque sphere it has not hit before, and a diffuse
-// or mirror bounce leaves outward -- so, by induction, only dielectric
-// spheres are ever entered (up to the fp32 rounding of a hit point next to a
-// contact between two spheres, where the outside-only root lets the ray
-// leave, as in exact arithmetic).
-bool outside_only(const ptg_sphere &s, const ptg_camera *cam)
-{
-    double d2 = 0.0, p2 = 0.0;
-    for (int c = 0; c < 3; ++c) {
-        const double t = s.position[c] - cam->position[c];
-        d2 += t * t;
-        p2 += cam->position[c] * cam->position[c];
-    }
-    // margins: the lens bound's, the fp32 rounding of a camera origin, the
-    // double rounding of d2
-    const double reach = s.radius + 2.0001 * cam->lens_radius + 1e-6 * (1.0 + std::sqrt(p2)) + 1e-9 * s.radius;
-    return s.material != PTG_DIELECTRIC && d2 > reach * reach;
-}
-
-// KArgs::room_nmr.  The kernel's up = fl(plane_plus - o_k) >= -m implies
-// plane_plus - o_k >= -m (1 + 2^-23) (a rounding of at most half an ulp of a
-// difference near -m; a larger difference passes or fails with its sign), so
-// with m = gap (1 - 2^-10) the origin lies below plane_plus + gap =
-// pair_hi; the same for um and pair_lo.  Open sides (planes at +-inf, up or
-// um = +inf) bound nothing, as their +-kFarPlane bounds (unreachable) did.
-float room_neg_margin(const KArgs &A)
-{
-    double gap = HUGE_VAL;
-    for (int k = 0; k < 3; ++k) {
-        if (A.plane_plus[k] < HUGE_VALF)
-            gap = std::min(gap, (double)A.pair_hi[k] - (double)A.plane_plus[k]);
-        if (A.plane_minus[k] > -HUGE_VALF)
-            gap = std::min(gap, (double)A.plane_minus[k] - (double)A.pair_lo[k]);
-    }
-    if (!(gap > 0.0) || gap == HUGE_VAL)
-        return HUGE_VALF;  // no lane counts as inside: every wave takes the exact per-axis checks
-    const float m = (float)(gap * (1.0 - 0x1p-10));
-    return -std::nextafter(m, 0.0f);
-}
-
-void box_mode_of(const ptg_sphere *s, int n, const ptg_camera *cam, const std::vector<int> &axis,
-                 const std::vector<GeoRec> &geo, const std::vector<int> &order, KArgs &A)
-{
-    A.box_mode = 0;
-    A.box_walls_out = 0;
-    int cnt[3] = {0, 0, 0}, general = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!is_huge(s[i], cam))
-            continue;
-        if (axis[i] < 0)
-            ++general;
-        else
-            ++cnt[axis[i]];
-    }
-    bool ok = general == 0 && (A.pairs[0] || A.pairs[1] || A.pairs[2]);
-    for (int k = 0; k < 3; ++k)
-        ok = ok && (A.pairs[k] ? cnt[k] == 2 : cnt[k] <= 1);
-    const SceneBox box = scene_box(s, n, cam);
-    for (int i = 0; i < n && ok; ++i)  // single walls too (the pairs' members are clear)
-        if (is_huge(s[i], cam) && axis[i] >= 0)
-            ok = wall_clear(s, i, axis[i], (&geo[i].g1.x)[axis[i]] < 0.0f, cam, box);
-    if (!ok)
-        return;
-    const double margin = 1e-4 * std::max(1.0, box.diag);
-    for (int k = 0; k < 3; ++k) {
-        A.rec_plus[k] = A.rec_minus[k] = -1;
-        A.plane_plus[k] = HUGE_VALF;  // missing wall: never the nearest plane, never needed
-        A.plane_minus[k] = -HUGE_VALF;
-        const int begin = k == 0 ? 0 : A.end_ax[k - 1];
-        for (int j = begin; j < A.end_ax[k]; ++j) {
-            const int i = order[j];
-            const float nk = (&geo[i].g1.x)[k];  // anchor normal component: exactly +-1
-            const float plane = (&geo[i].g0.x)[k];  // the anchor point's coordinate
-            if (nk < 0.0f) {  // centre on the + side
-                A.rec_plus[k] = j * (int)sizeof(LinRec);
-                A.plane_plus[k] = plane;
-                if (!A.pairs[k])
-                    A.pair_hi[k] = (float)(s[i].position[k] - s[i].radius + margin);
-            } else {
-                A.rec_minus[k] = j * (int)sizeof(LinRec);
-                A.plane_minus[k] = plane;
-                if (!A.pairs[k])
-                    A.pair_lo[k] = (float)(s[i].position[k] + s[i].radius - margin);
-            }
-        }
-        if (A.rec_plus[k] < 0)
-            A.pair_hi[k] = kFarPlane;
-        if (A.rec_minus[k] < 0)
-            A.pair_lo[k] = -kFarPlane;
-    }
-    A.box_mode = 1;
-    A.box_walls_out = 1;
-    for (int i = 0; i < n; ++i)
-        if (is_huge(s[i], cam) && axis[i] >= 0 && !outside_only(s[i], cam))
-            A.box_walls_out = 0;
-}
-
-
-// Linear scenes: scan order (scene_scan) -- huge spheres anchored on x, y, z
-// (each axis group led by its wall pair, + wall first), then the other huge
-// spheres, then the small ones, each group otherwise in scene index order;
-// end_ax / end_big / pairs receive the group ends and pair flags.
-std::vector<int> scan_order_of(const ptg_sphere *s, int n, const ptg_camera *cam, const std::vector<int> &axis,
-                               const std::vector<GeoRec> &geo, KArgs &A)
-{
-    std::vector<int> order;
-    int plus[3], minus[3];
-    pair_walls(s, n, axis, geo, cam, scene_box(s, n, cam), plus, minus, A.pair_lo, A.pair_hi);
-    for (int k = 0; k < 3; ++k) {
-        A.pairs[k] = plus[k] >= 0 ? 1 : 0;
-        if (A.pairs[k]) {
-            order.push_back(plus[k]);
-            order.push_back(minus[k]);
-        }
-        for (int i = 0; i < n; ++i)
-            if (axis[i] == k && i != plus[k] && i != minus[k])
-                order.push_back(i);
-        A.end_ax[k] = (int)order.size();
-    }
-    box_mode_of(s, n, cam, axis, geo, order, A);
-    for (int i = 0; i < n; ++i)
-        if (is_huge(s[i], cam) && axis[i] < 0)
-            order.push_back(i);
-    A.end_big = (int)order.size();
-    for (int i = 0; i < n; ++i)
-        if (!is_huge(s[i], cam))
-            order.push_back(i);
-    return order;
-}
-
-
-// Records in scan order.  Axis-anchored records carry the signs in their
-// constants: g0.w = s R, g1.w = s 2R (the kernel reads e_k and d_k).
-void prepare_scan_order(const ptg_sphere *s, int n, const ptg_camera *cam, const std::vector<GeoRec> &geo,
-                        const std::vector<ShadeRec> &shade, const std::vector<int> &axis,
-                        std::vector<GeoRec> &lgeo, std::vector<ShadeRec> &lshade, KArgs &A)
-{
-    lgeo.clear();
-    lshade.clear();
-    for (int i : scan_order_of(s, n, cam, axis, geo, A)) {
-        GeoRec g = geo[i];
-        if (axis[i] >= 0) {
-            const float sgn = (&g.g1.x)[axis[i]];  // +-1 exactly
-            g.g0.w = sgn * g.g0.w;
-            g.g1.w = sgn * g.g1.w;
-        }
-        lgeo.push_back(g);
-        lshade.push_back(shade[i]);
-    }
-}
-
-int check_params(const ptg_params *p)
-{
-    if (!p)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "params is NULL");
-    if (p->width <= 0 || p->height <= 0)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (p->samples < 0)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "samples must be >= 0");
-    if (p->num_subpixels < 1 || p->num_subpixels > 8)
-        return fail(PTG_ERR_UNSUPPORTED, "num_subpixels must be in [1, 8]");
-    if (p->band_rows < 1 || p->shard_count < 1 || p->shard_rank < 0 || p->shard_rank >= p->shard_count)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "invalid shard (band_rows >= 1, 0 <= rank < count)");
-    if ((int64_t)p->width * p->height > (int64_t)1 << 28 || p->width >= (1 << 20))
-        return fail(PTG_ERR_UNSUPPORTED, "image too large");
-    return PTG_OK;
-}
-
-// Launch geometry for samples [s_begin, s_end) of every sub-pixel.
-int fill_launch(const ptg_context *ctx, const ptg_params *p, KArgs &A, int &grid, int s_begin = 0, int s_end = -1,
-                bool accumulate_only = false)
-{
-    if (s_end < 0)
-        s_end = p->samples;
-    const int nsamp = s_end - s_begin;
-    A = ctx->base;
-    A.W = p->width;
-    A.H = p->height;
-    A.samps = p->samples;
-    A.nsub = p->num_subpixels;
-    A.lanes_per_pixel = p->num_subpixels * p->num_subpixels;
-    A.pixels_per_wave = 64 / A.lanes_per_pixel;
-    A.waves_per_row = (p->width + A.pixels_per_wave - 1) / A.pixels_per_wave;
-    int bands = (p->height + p->band_rows - 1) / p->band_rows;
-    A.slab_rows = ((bands + p->shard_count - 1) / p->shard_count) * p->band_rows;
-    A.band_rows = p->band_rows;
-    A.shard_rank = p->shard_rank;
-    A.shard_count = p->shard_count;
-    A.invW = 1.0f / (float)p->width;
-    A.invH = 1.0f / (float)p->height;
-    A.inv_samps = p->samples > 0 ? 1.0f / (float)p->samples : 0.0f;
-    A.sub_len = 1.0f / (float)p->num_subpixels;
-    A.inv_sub2 = 1.0f / (float)(p->num_subpixels * p->num_subpixels);
-    A.seed = p->seed;
-    A.sample_begin = s_begin;
-    A.sample_end = s_end;
-    A.keep_acc = 0;
-    A.count_tests = (p->flags & PTG_FLAG_COUNT_TESTS) != 0;
-    A.count_nonfinite = (p->flags & PTG_FLAG_COUNT_NONFINITE) != 0;
-    A.exact_math = (p->flags & PTG_FLAG_EXACT_MATH) != 0;
-    if (!A.exact_math && !A.box_walls_out)
-        A.box_mode = 0;  // the fast mode's box-mode wall test assumes rays outside the walls
-    // work unit = pixel group x chunk of samples.  Auto: split the samples
-    // only as far as needed for ~96k work units (about 16 waves per SIMD slot
-    // on 256 CUs), which keeps the grid-level tail small at any GPU count.
-    // Below the split-tail threshold, BVH scenes aim at PTG_BVH_UNIT_MULT
-    // times more units: their cost varies strongly over the image (sky rows
-    // vs the sphere field).
-    const int groups = A.slab_rows * A.waves_per_row;
-    // split tail (below) from PTG_TAIL_MIN_HALF_ROUNDS/2 rounds of the
-    // device's wave slots on, BVH scenes from PTG_BVH_TAIL_MIN_HALF_ROUNDS/2
-    // (then the head runs whole-pixel units even where ~96k units would split
-    // samples, e.g. an 8-GPU shard).  The head's units are whole pixels, so
-    // the head needs enough rounds to average out the rows' different costs:
-    // at 2 rounds (8-way shards of the bench frame) the split tail gains
-    // 1.7-2.1 % on the box scenes but loses 28 % on the 10,000-sphere scene
-    // (tools/scene_shard_ab.sh); from 4 rounds on it gains on both.
-    const long long tail_min = (long long)(ctx->n > kLinearMax ? PTG_BVH_TAIL_MIN_HALF_ROUNDS : PTG_TAIL_MIN_HALF_ROUNDS) *
-                               ctx->wave_slots / 2;
-    const bool tail_ok = p->chunk_samples <= 0 && !accumulate_only && s_begin == 0 && s_end == p->samples &&
-                         PTG_TAIL_CHUNKS > 1 && nsamp >= PTG_TAIL_CHUNKS && nsamp <= kMaxChunk && groups >= tail_min;
-    int chunk = p->chunk_samples;
-    if (tail_ok) {
-        chunk = nsamp;
-    } else if (chunk <= 0) {
-        // (linear scenes: PTG_UNIT_ROUNDS rounds of the device's wave slots --
-        // C1's 7,500 pixel groups in 6-sample units, 22,500 units: 12 %
-        // faster than ~96k units of 2 samples, whose per-unit setup weighed)
-        const long long target =
-            ctx->n > kLinearMax ? PTG_BVH_UNIT_MULT * 98304 : (long long)PTG_UNIT_ROUNDS * ctx->wave_slots;
-        long long want = (target + groups - 1) / groups;
-        long long nch = want < 1 ? 1 : (want > nsamp ? nsamp : want);
-        chunk = nch > 0 ? (int)((nsamp + nch - 1) / nch) : 1;
-    }
-    if (chunk > nsamp)
-        chunk = nsamp > 0 ? nsamp : 1;
-    if (chunk > kMaxChunk)  // the kernel's divmod_nv needs 64 * chunk <= 2^22 (the image does not depend on it)
-        chunk = kMaxChunk;
-    A.chunk = chunk;
-    A.n_groups = groups;
-    int n_chunks = nsamp > 0 ? (nsamp + chunk - 1) / chunk : 0;
-    // in-wave resolve only when one unit holds ALL samples of its pixels
-    A.single_chunk = !accumulate_only && n_chunks <= 1 && s_begin == 0 && s_end == p->samples;
-    A.n_units = (long long)A.n_groups * n_chunks;
-    A.n_levels = 1;
-    A.lvl_group[0] = 0;
-    A.lvl_group[1] = groups;
-    A.lvl_chunk[0] = chunk;
-    A.lvl_unit[0] = 0;
-    A.lvl_unit[1] = A.n_units;
-    for (int l = 0; l < kMaxLevels; ++l) {
-        A.lvl_coop[l] = 0;
-        A.lvl_psplit[l] = 1;
-        A.lvl_inwave[l] = 0;
-    }
-    A.lvl_inwave[0] = A.single_chunk;
-    A.resolve_row0 = 0;
-    A.needs_resolve = !A.single_chunk;
-    // Split tail: with whole-pixel units, the grid ends when its slowest last
-    // units end (a unit is ~1/16 of the frame per wave slot here).  The last
-    // rows -- about one round of the device's wave slots -- run instead as
-    // shorter units, accumulated and resolved by resolve_kernel; everything
-    // before keeps the in-wave resolve.  The tail's rows get shorter units
-    // towards the end (PTG_TAIL_LEVELS levels: the first half of the tail
-    // rows in PTG_TAIL_CHUNKS... chunks, see tail_level_chunks), so the last
-    // units to start are the shortest.
-    if (tail_ok && A.single_chunk) {
-        const long long tail_slots = (long long)(ctx->n > kLinearMax ? PTG_BVH_TAIL_HALF_ROUNDS : PTG_LIN_TAIL_HALF_ROUNDS) *
-                                     ctx->wave_slots / 2;
-        int tail_rows = (int)((tail_slots + A.waves_per_row - 1) / A.waves_per_row);
-        tail_rows = tail_rows < A.slab_rows ? tail_rows : A.slab_rows;
-        const bool many = groups >= 5LL * ctx->wave_slots;
-        // level row counts: halves of what is left, the last level takes the rest
-        int rows_left = tail_rows, row = A.slab_rows - tail_rows;
-        A.resolve_row0 = A.slab_rows;  // no accumulating level yet
-        A.lvl_group[1] = row * A.waves_per_row;
-        A.lvl_unit[1] = A.lvl_group[1];  // head: one unit per group
-        int l = 1;
-        constexpr int kLinWaves = kBlock / 64;
-        for (; l <= PTG_TAIL_LEVELS && rows_left > 0; ++l) {
-            const int rows = l == PTG_TAIL_LEVELS ? rows_left : (rows_left + 1) / 2;
-            const int tc = (many ? (ctx->n > kLinearMax ? PTG_BVH_TAIL_CHUNKS_MANY : PTG_TAIL_CHUNKS_MANY)
-                                 : PTG_TAIL_CHUNKS) << (l - 1);
-            const int ch = (nsamp + tc - 1) / tc;
-            const int nch = (nsamp + ch - 1) / ch;
-            // one chunk per wave of a (linear-kernel) workgroup: the level's
-            // sums stay in LDS; its first unit starts a workgroup
-            const bool coop = ctx->n <= kLinearMax && nch == kLinWaves;
-            // BVH kernel (one wave per workgroup, no cooperative level): the
-            // pixel group split into as many units of interleaved pixels,
-            // each with every sample -- the unit length of nch sample chunks,
-            // resolved in the wave (C5: no HBM atomics, no resolve pass)
-            const bool psplit = !coop && ctx->n > kLinearMax && l == 1 && nch > 1 &&
-                                A.pixels_per_wave >= nch;
-            if (coop)
-                A.lvl_unit[l] = (A.lvl_unit[l] + kLinWaves - 1) / kLinWaves * kLinWaves;
-            else if (!psplit && A.resolve_row0 == A.slab_rows)
-                A.resolve_row0 = row;
-            A.lvl_coop[l] = coop ? 1 : 0;
-            A.lvl_psplit[l] = psplit ? nch : 1;
-            A.lvl_inwave[l] = psplit ? 1 : 0;
-            row += rows;
-            rows_left -= rows;
-            A.lvl_chunk[l] = psplit ? nsamp : ch;
-            A.lvl_group[l + 1] = row * A.waves_per_row;
-            A.lvl_unit[l + 1] = A.lvl_unit[l] + (long long)(A.lvl_group[l + 1] - A.lvl_group[l]) * nch;
-        }
-        A.n_levels = l;
-        A.n_units = A.lvl_unit[l];
-        A.needs_resolve = A.resolve_row0 < A.slab_rows;
-        if (!A.needs_resolve)
-            A.resolve_row0 = 0;
-    }
-#if PTG_BVH_HEAD_CHUNK > 0
-    // BVH frames/shards below their split-tail threshold (e.g. 8-way shards
-    // of C5): the head rows run in longer sample chunks -- fewer per-unit
-    // pool tails -- and about the last round of wave slots' rows in the auto
-    // chunk, so the grid still ends on short units.  Every unit accumulates;
-    // resolve_kernel finishes all rows.
-    else if (ctx->n > kLinearMax && p->chunk_samples <= 0 && !accumulate_only && s_begin == 0 &&
-             s_end == p->samples && chunk < PTG_BVH_HEAD_CHUNK && chunk < nsamp) {
-        const long long tslots = (long long)PTG_BVH_HEAD_TAIL_HALF_ROUNDS * ctx->wave_slots / 2;
-        int tail_rows = (int)((tslots + A.waves_per_row - 1) / A.waves_per_row);
-        if (tail_rows < A.slab_rows) {
-            const int hc = PTG_BVH_HEAD_CHUNK < nsamp ? PTG_BVH_HEAD_CHUNK : nsamp;
-            const int hn = (nsamp + hc - 1) / hc;
-            const int row = A.slab_rows - tail_rows;
-            A.lvl_chunk[0] = hc;
-            A.lvl_group[1] = row * A.waves_per_row;
-            A.lvl_unit[1] = (long long)A.lvl_group[1] * hn;
-            const int tc = PTG_BVH_TAIL_CHUNK > 0 ? (PTG_BVH_TAIL_CHUNK < nsamp ? PTG_BVH_TAIL_CHUNK : nsamp) : chunk;
-            const int tn = (nsamp + tc - 1) / tc;
-            A.lvl_chunk[1] = tc;
-            A.lvl_group[2] = groups;
-            A.lvl_unit[2] = A.lvl_unit[1] + (long long)(groups - A.lvl_group[1]) * tn;
-            A.n_levels = 2;
-            A.n_units = A.lvl_unit[2];
-            A.needs_resolve = 1;
-        }
-    }
-#endif
-    const int waves_per_block = (ctx->n > kLinearMax ? PTG_BVH_BLOCK : kBlock) / 64;
-    const long long g = (A.n_units + waves_per_block - 1) / waves_per_block;  // 64-bit before any cast
-    grid = 0;
-    if (g > 0x7FFFFFFFLL)
-        return fail(PTG_ERR_UNSUPPORTED, "too many work units (" + std::to_string(A.n_units) +
-                                             "): raise chunk_samples or use 0 (auto)");
-    grid = (int)g;
-    return PTG_OK;
-}
-
 int set_device(int device)
 {
     int count = 0;
@@ -2754,6 +2008,35 @@ int set_device(int device)
         PTG_HIP(hipSetDevice(device));
     return PTG_OK;
 }
+
+// ptg_context_create: one of the context's device tables, allocated and filled
+template <typename T>
+int upload(T *&dst, const void *src, size_t bytes, const char *what)
+{
+    if (hipMalloc(&dst, bytes) != hipSuccess)
+        return fail(PTG_ERR_OUT_OF_MEMORY, std::string("hipMalloc of ") + what + " failed");
+    PTG_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return PTG_OK;
+}
+
+#if PTG_BLOCK_STATS
+// a 256 x 16 block-counter array (ptg_dbg_stats, ptg_dbg_stats2) summed over its slots, then zeroed
+template <typename Sym>
+int read_block_stats(const Sym &sym, unsigned long long *out16)
+{
+    std::vector<unsigned long long> h(256 * 16);
+    PTG_HIP(hipDeviceSynchronize());
+    PTG_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(sym), h.size() * sizeof(h[0])));
+    for (int i = 0; i < 16; ++i) {
+        out16[i] = 0;
+        for (int b = 0; b < 256; ++b)
+            out16[i] += h[b * 16 + i];
+    }
+    std::vector<unsigned long long> z(h.size(), 0ull);
+    PTG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(sym), z.data(), z.size() * sizeof(z[0])));
+    return PTG_OK;
+}
+#endif
 
 }  // namespace
 
@@ -2779,34 +2062,8 @@ int ptg_unit_trace_(unsigned long long *out, int n_units)
 #endif
 #if PTG_BLOCK_STATS
 // debug builds only: the 16 block counters summed over their 256 slots (then zeroed)
-int ptg_debug_stats2_(unsigned long long *out16)
-{
-    std::vector<unsigned long long> h(256 * 16);
-    PTG_HIP(hipDeviceSynchronize());
-    PTG_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(ptg_dbg_stats2), h.size() * sizeof(h[0])));
-    for (int i = 0; i < 16; ++i) {
-        out16[i] = 0;
-        for (int b = 0; b < 256; ++b)
-            out16[i] += h[b * 16 + i];
-    }
-    std::vector<unsigned long long> z(h.size(), 0ull);
-    PTG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(ptg_dbg_stats2), z.data(), z.size() * sizeof(z[0])));
-    return PTG_OK;
-}
-int ptg_debug_stats_(unsigned long long *out16)
-{
-    std::vector<unsigned long long> h(256 * 16);
-    PTG_HIP(hipDeviceSynchronize());
-    PTG_HIP(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(ptg_dbg_stats), h.size() * sizeof(h[0])));
-    for (int i = 0; i < 16; ++i) {
-        out16[i] = 0;
-        for (int b = 0; b < 256; ++b)
-            out16[i] += h[b * 16 + i];
-    }
-    std::vector<unsigned long long> z(h.size(), 0ull);
-    PTG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(ptg_dbg_stats), z.data(), z.size() * sizeof(z[0])));
-    return PTG_OK;
-}
+int ptg_debug_stats2_(unsigned long long *out16) { return read_block_stats(ptg_dbg_stats2, out16); }
+int ptg_debug_stats_(unsigned long long *out16) { return read_block_stats(ptg_dbg_stats, out16); }
 #endif
 
 const char *ptg_last_error(void) { return g_last_error.c_str(); }
@@ -2825,8 +2082,7 @@ int ptg_shard_rows(int32_t height, int32_t band_rows, int32_t shard_count, int32
 {
     if (!rows || height <= 0 || band_rows <= 0 || shard_count <= 0)
         return fail(PTG_ERR_INVALID_ARGUMENT, "invalid shard geometry");
-    int bands = (height + band_rows - 1) / band_rows;
-    *rows = ((bands + shard_count - 1) / shard_count) * band_rows;
+    *rows = shard_slab_rows(height, band_rows, shard_count);
     return PTG_OK;
 }
 
@@ -2846,185 +2102,61 @@ int ptg_context_create(const ptg_sphere *spheres, size_t n_spheres, const ptg_ca
         return rc;
     int dev = 0;
     PTG_HIP(hipGetDevice(&dev));
-    std::vector<GeoRec> geo, lgeo;
-    std::vector<ShadeRec> shade, lshade;
-    std::vector<int> axis;
-    prepare_scene(spheres, (int)n_spheres, cam, geo, shade, axis);
-    KArgs order{};
-    const bool linear = (int)n_spheres <= kLinearMax;
-    std::vector<LinRec> lin;
-    if (linear) {  // the scan's record order, interleaved, + the no-hit sentinel
-        prepare_scan_order(spheres, (int)n_spheres, cam, geo, shade, axis, lgeo, lshade, order);
-        lin.resize(n_spheres + 2 + 2);  // + the box-mode wall table(s) (scene_scan)
-        std::memset(lin.data(), 0, lin.size() * sizeof(LinRec));
-        for (size_t i = 0; i < n_spheres; ++i)
-            lin[i] = LinRec{lgeo[i], lshade[i]};
-        int32_t walls[6];
-        for (int k = 0; k < 3; ++k) {
-            walls[2 * k] = order.rec_plus[k];
-            walls[2 * k + 1] = order.rec_minus[k];
-        }
-        std::memcpy(&lin[n_spheres + 1], walls, sizeof(walls));
-        // entry 2 k + side: the wall's geometry, g1.x = its record's byte
-        // offset; a missing wall: NaN geometry (its test never wins), offset 0
-        GeoRec wg[6];
-        for (int e = 0; e < 6; ++e) {
-            const float qnan = __builtin_nanf("");
-            const int off = walls[e];
-            if (order.box_mode && off >= 0 && off / (int)sizeof(LinRec) < (int)n_spheres) {
-                wg[e] = lgeo[off / (int)sizeof(LinRec)];
-                // the record's byte offset from the sentinel (scene_scan's
-                // winner bi)
-                const int32_t tag = (off / (int)sizeof(LinRec) - (int)n_spheres) * (int)sizeof(LinRec);
-                std::memcpy(&wg[e].g1.x, &tag, 4);
-            } else {
-                wg[e].g0 = make_float4(qnan, qnan, qnan, qnan);
-                wg[e].g1 = make_float4(0.0f, qnan, qnan, qnan);
-            }
-        }
-        static_assert(sizeof(wg) <= 2 * sizeof(LinRec), "wall geometry table size");
-        std::memcpy(&lin[n_spheres + 2], wg, sizeof(wg));
-    }
-    ptg_context *ctx = new ptg_context();
+    ptg_context *ctx = new ptg_context();  // zeroed, base included
     ctx->device = dev;
     {
         hipDeviceProp_t prop;
         ctx->wave_slots = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount * 32 : 8192;
     }
-    ctx->n = (int)n_spheres;
-    // linear scenes: d_lin; BVH scenes: d_shade (scene index order) + d_bvh
-    const size_t bytes = linear ? lin.size() * sizeof(LinRec) : std::max<size_t>(n_spheres, 1) * sizeof(ShadeRec);
-    if (hipMalloc(linear ? (void **)&ctx->d_lin : (void **)&ctx->d_shade, bytes) != hipSuccess) {
-        delete ctx;
-        return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the scene failed");
-    }
-    if (linear)
-        PTG_HIP_OR_DESTROY(hipMemcpy(ctx->d_lin, lin.data(), bytes, hipMemcpyHostToDevice));
-    else if (n_spheres) {
-        std::vector<ShadeRec> up(shade.begin(), shade.begin() + n_spheres);
-        PTG_HIP_OR_DESTROY(hipMemcpy(ctx->d_shade, up.data(), n_spheres * sizeof(ShadeRec), hipMemcpyHostToDevice));
-    }
-    {
-        float tab[2 * kTrigEntries];
-        trig_table(tab);
-        if (hipMalloc(&ctx->d_trig, sizeof(tab)) != hipSuccess) {
-            ptg_context_destroy(ctx);
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the sin/cos table failed");
-        }
-        PTG_HIP_OR_DESTROY(hipMemcpy(ctx->d_trig, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
+    const int n = ctx->n = (int)n_spheres;
     ctx->cam64 = *cam;
-    if (n_spheres) {
-        if (hipMalloc(&ctx->d_sph64, n_spheres * sizeof(ptg_sphere)) != hipSuccess) {
-            ptg_context_destroy(ctx);
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the scene (f64) failed");
-        }
-        PTG_HIP_OR_DESTROY(hipMemcpy(ctx->d_sph64, spheres, n_spheres * sizeof(ptg_sphere), hipMemcpyHostToDevice));
-    }
     KArgs &A = ctx->base;
-    std::memset(&A, 0, sizeof(A));
+    // prepare (scene_prep.hpp): the upload tables; the scan layout goes straight into A
+    const bool linear = n <= kLinearMax;
+    const SceneRecs sc = prepare_scene(spheres, n, cam);
+    std::vector<LinRec> lin;
+    BvhUpload bvh;
+    if (linear)
+        lin = prepare_linear_upload(spheres, n, cam, sc, A);
+    else
+        bvh = prepare_bvh_upload(spheres, n, cam, sc.geo);
+    float trig[2 * kTrigEntries];
+    trig_table(trig);
+    // allocate and upload.  linear scenes: d_lin; BVH scenes: d_shade (scene index order) + d_bvh
+    rc = linear ? upload(ctx->d_lin, lin.data(), lin.size() * sizeof(LinRec), "the scene")
+                : upload(ctx->d_shade, sc.shade.data(), (size_t)n * sizeof(ShadeRec), "the scene");
+    if (!rc)
+        rc = upload(ctx->d_trig, trig, sizeof(trig), "the sin/cos table");
+    if (!rc && n)
+        rc = upload(ctx->d_sph64, spheres, (size_t)n * sizeof(ptg_sphere), "the scene (f64)");
+    if (!rc && !linear)
+        rc = upload(ctx->d_bvh, bvh.blob.data(), bvh.blob.size(), "the BVH");
+    if (rc) {
+        ptg_context_destroy(ctx);
+        return rc;
+    }
+    // the scene and camera fields of every launch's KArgs
     A.trig = ctx->d_trig;
     A.lin = ctx->d_lin;
     A.shade = ctx->d_shade;
-    A.n = (int)n_spheres;
-    for (int k = 0; k < 3; ++k) {
-        A.end_ax[k] = order.end_ax[k];
-        A.pairs[k] = order.pairs[k];
-        A.pair_lo[k] = order.pair_lo[k];
-        A.pair_hi[k] = order.pair_hi[k];
-        A.rec_plus[k] = order.rec_plus[k];
-        A.rec_minus[k] = order.rec_minus[k];
-        A.plane_plus[k] = order.plane_plus[k];
-        A.plane_minus[k] = order.plane_minus[k];
-    }
-    A.box_mode = order.box_mode;
-    A.end_big = order.end_big;
-    A.box_walls_out = order.box_walls_out;
+    A.n = n;
     A.room_nmr = room_neg_margin(A);
-    if ((int)n_spheres > kLinearMax) {
-        std::vector<char> huge(n_spheres);
-        for (size_t i = 0; i < n_spheres; ++i)
-            huge[i] = is_huge(spheres[i], cam);
-        BvhBuild b = build_bvh(spheres, (int)n_spheres, huge);
-        const size_t n_leaf = b.order.size(), n_big = b.big.size();
-        // one allocation: leaf records | leaf ids | huge spheres | their ids |
-        // the 8 interleaved wide layouts | their continuations
-        const size_t off_geo = 0;
-        const size_t off_id = off_geo + n_leaf * sizeof(float4);
-        const size_t off_bgeo = (off_id + n_leaf * sizeof(int) + 15) & ~size_t(15);
-        const size_t off_bid = off_bgeo + n_big * sizeof(GeoRec);
-        const size_t off_q = (off_bid + n_big * sizeof(int) + 15) & ~size_t(15);
-        const size_t n_recs = wide_bvh(b, 0, 0).size();  // records per layout
-        // near-plane-first boxes: one layout per octant
-        const size_t n_layouts = 8;
-        const size_t stride = n_recs;  // (interleaved: 8 x n_recs records in all, no layout stride)
-        const size_t off_cont = off_q + n_layouts * stride * sizeof(BvhNodeQ);
-        const size_t total = off_cont + n_layouts * stride / kWide * sizeof(int32_t) + 16;
-        std::vector<unsigned char> blob(total, 0);
-        // the 8 layouts interleaved node by node: node j of layout k at
-        // interleaved node 8 j + k, so the copies of one node share a 512-B
-        // block instead of aliasing a power of two of records apart
-        {
-            auto ilv = [](int32_t local, int k) { return ((local >> 2) * 8 + k) * 4 + (local & 3); };
-            for (int k = 0; k < 8; ++k) {
-                std::vector<BvhNodeQ> qk = wide_bvh(b, k, 0);
-                const std::vector<int32_t> ck = wide_conts(qk, 0);
-                for (size_t r = 0; r < qk.size(); ++r) {
-                    BvhNodeQ &z = qk[r];
-                    if (z.word >= 0)
-                        z.word = ilv(z.word, k);
-                    std::memcpy(blob.data() + off_q + (size_t)ilv((int32_t)r, k) * sizeof(BvhNodeQ), &z, sizeof(z));
-                }
-                for (size_t j = 0; j < ck.size(); ++j) {
-                    const int32_t c = ck[j] >= 0 ? ilv(ck[j], k) : ck[j];
-                    std::memcpy(blob.data() + off_cont + (j * 8 + (size_t)k) * sizeof(int32_t), &c, sizeof(c));
-                }
-            }
-        }
-        const WideGrid wg(b.nodes.empty() ? BvhNodeHost{} : b.nodes[0]);
+    if (!linear) {
+        const unsigned char *blob = static_cast<const unsigned char *>(ctx->d_bvh);
+        A.bvh_qnodes = reinterpret_cast<const uint4 *>(blob + bvh.off_q);
+        A.bvh_cont = reinterpret_cast<const int *>(blob + bvh.off_cont);
+        A.bvh_sph = reinterpret_cast<const float4 *>(blob + bvh.off_geo);
+        A.bvh_id = reinterpret_cast<const int *>(blob + bvh.off_id);
+        A.big_geo = reinterpret_cast<const GeoRec *>(blob + bvh.off_bgeo);
+        A.big_id = reinterpret_cast<const int *>(blob + bvh.off_bid);
         for (int c = 0; c < 3; ++c) {
-            A.q_lo[c] = wg.centre[c];
-            A.q_scale[c] = wg.scale[c];
+            A.q_lo[c] = bvh.q_lo[c];
+            A.q_scale[c] = bvh.q_scale[c];
         }
-        for (size_t i = 0; i < n_leaf; ++i) {
-            const ptg_sphere &sp = spheres[b.order[i]];  // leaf record {C, -R^2}, as the GeoRec of a small sphere
-            const float4 rec = make_float4((float)sp.position[0], (float)sp.position[1], (float)sp.position[2],
-                                           (float)(-(sp.radius * sp.radius)));
-            std::memcpy(blob.data() + off_geo + i * sizeof(float4), &rec, sizeof(float4));
-            std::memcpy(blob.data() + off_id + i * sizeof(int), &b.order[i], sizeof(int));
-        }
-        for (size_t i = 0; i < n_big; ++i) {
-            std::memcpy(blob.data() + off_bgeo + i * sizeof(GeoRec), &geo[b.big[i]], sizeof(GeoRec));
-            std::memcpy(blob.data() + off_bid + i * sizeof(int), &b.big[i], sizeof(int));
-        }
-        if (hipMalloc(&ctx->d_bvh, total) != hipSuccess) {
-            ptg_context_destroy(ctx);
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the BVH failed");
-        }
-        PTG_HIP_OR_DESTROY(hipMemcpy(ctx->d_bvh, blob.data(), total, hipMemcpyHostToDevice));
-        unsigned char *base = static_cast<unsigned char *>(ctx->d_bvh);
-        A.bvh_qnodes = reinterpret_cast<const uint4 *>(base + off_q);
-        A.bvh_cont = reinterpret_cast<const int *>(base + off_cont);
-        A.bvh_sph = reinterpret_cast<const float4 *>(base + off_geo);
-        A.bvh_id = reinterpret_cast<const int *>(base + off_id);
-        A.big_geo = reinterpret_cast<const GeoRec *>(base + off_bgeo);
-        A.big_id = reinterpret_cast<const int *>(base + off_bid);
-        A.n_nodes = (int)n_recs;
-        A.n_big = (int)n_big;
+        A.n_nodes = bvh.n_nodes;
+        A.n_big = bvh.n_big;
     }
-    A.pos_x = (float)cam->position[0];
-    A.pos_y = (float)cam->position[1];
-    A.pos_z = (float)cam->position[2];
-    A.base_x = (float)(cam->lower_left_corner[0] - cam->position[0]);
-    A.base_y = (float)(cam->lower_left_corner[1] - cam->position[1]);
-    A.base_z = (float)(cam->lower_left_corner[2] - cam->position[2]);
-    A.X_x = (float)cam->cam_x_axis[0];
-    A.X_y = (float)cam->cam_x_axis[1];
-    A.X_z = (float)cam->cam_x_axis[2];
-    A.Y_x = (float)cam->cam_y_axis[0];
-    A.Y_y = (float)cam->cam_y_axis[1];
-    A.Y_z = (float)cam->cam_y_axis[2];
-    A.lens = (float)cam->lens_radius;
+    prepare_camera(cam, A);
     *out = ctx;
     return PTG_OK;
 }
@@ -3037,16 +2169,13 @@ int ptg_scene_layout(const ptg_sphere *spheres, size_t n_spheres, const ptg_came
     if (n_spheres > (size_t)(1 << 24))
         return fail(PTG_ERR_UNSUPPORTED, "too many spheres");
     const int n = (int)n_spheres;
-    std::vector<GeoRec> geo;
-    std::vector<ShadeRec> shade;
-    std::vector<int> axis;
-    prepare_scene(spheres, n, cam, geo, shade, axis);
+    const SceneRecs sc = prepare_scene(spheres, n, cam);
     KArgs ends{};
     std::vector<int> order;
     if (n <= kLinearMax)
-        order = scan_order_of(spheres, n, cam, axis, geo, ends);
+        order = scan_order_of(spheres, n, cam, sc, ends);
     for (int i = 0; i < n; ++i)
-        anchor_axis[i] = axis[i];
+        anchor_axis[i] = sc.axis[i];
     for (int k = 0; k < 3 && n <= kLinearMax; ++k)
         if (ends.pairs[k])  // the pair leads axis k's group
             anchor_axis[order[k == 0 ? 0 : ends.end_ax[k - 1]]] = anchor_axis[order[(k == 0 ? 0 : ends.end_ax[k - 1]) + 1]] = k + 3;
@@ -3102,6 +2231,17 @@ int ensure_acc(ptg_context *ctx, size_t need, hipStream_t stream)
 }
 
 size_t acc_elems_for(const KArgs &A) { return (size_t)A.slab_rows * A.W * A.lanes_per_pixel * 3; }
+
+// The device entry points' common start, after their argument checks: the
+// context's device current and the launch plan for samples [s_begin, s_end);
+// with_acc: the exact accumulator at the plan's size as well.
+int begin_launch(ptg_context *ctx, const ptg_params *p, KArgs &A, int &grid, hipStream_t s, bool with_acc,
+                 int s_begin = 0, int s_end = -1, bool accumulate_only = false)
+{
+    PTG_HIP(hipSetDevice(ctx->device));
+    const int rc = fill_launch(ctx->base, ctx->wave_slots, p, A, grid, s_begin, s_end, accumulate_only);
+    return rc || !with_acc ? rc : ensure_acc(ctx, acc_elems_for(A), s);
+}
 
 int launch_render(const KArgs &A, int grid, bool count, hipStream_t s)
 {
@@ -3181,16 +2321,15 @@ int ptg_render_device(ptg_context *ctx, const ptg_params *params, float *d_slab,
     int rc = check_params(params);
     if (rc)
         return rc;
-    PTG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
-    if ((rc = fill_launch(ctx, params, A, grid)))
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/false)))
         return rc;
     if (params->flags & PTG_FLAG_REFERENCE_F64)
-        return launch_ref64(ctx, A, nullptr, d_slab, d_segments, reinterpret_cast<hipStream_t>(stream));
+        return launch_ref64(ctx, A, nullptr, d_slab, d_segments, s);
     // several units per pixel, a split tail accumulated in HBM, or no samples at all
     const bool resolve = A.needs_resolve || grid == 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if ((rc = ensure_acc(ctx, resolve ? acc_elems_for(A) : 0, s)))
         return rc;
     A.out = d_slab;
@@ -3216,7 +2355,7 @@ int ptg_launch_info(ptg_context *ctx, const ptg_params *params, int64_t *info, i
         return rc;
     KArgs A;
     int grid = 0;
-    if ((rc = fill_launch(ctx, params, A, grid)))
+    if ((rc = fill_launch(ctx->base, ctx->wave_slots, params, A, grid)))
         return rc;
     const bool bvh = ctx->n > kLinearMax;
     const int64_t v[PTG_LAUNCH_INFO_COUNT] = {
@@ -3240,17 +2379,16 @@ int ptg_accumulate_device(ptg_context *ctx, const ptg_params *params, int32_t sa
     if (params->flags & PTG_FLAG_REFERENCE_F64)
         return fail(PTG_ERR_UNSUPPORTED, "progressive passes are fp32 only (the reference-arithmetic mode sums "
                                          "its samples sequentially, main.cpp:192)");
-    PTG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
-    if ((rc = fill_launch(ctx, params, A, grid, sample_begin, sample_end, /*accumulate_only=*/true)))
-        return rc;
-    if ((rc = ensure_acc(ctx, acc_elems_for(A), reinterpret_cast<hipStream_t>(stream))))
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true, sample_begin, sample_end,
+                           /*accumulate_only=*/true)))
         return rc;
     A.acc = ctx->d_acc;
     A.segments = d_segments;
     ctx->acc_dirty = true;
-    return launch_render(A, grid, d_segments != nullptr, reinterpret_cast<hipStream_t>(stream));
+    return launch_render(A, grid, d_segments != nullptr, s);
 }
 
 int ptg_resolve_device(ptg_context *ctx, const ptg_params *params, int32_t samples_done, float *d_slab, void *stream)
@@ -3262,19 +2400,17 @@ int ptg_resolve_device(ptg_context *ctx, const ptg_params *params, int32_t sampl
         return rc;
     if (samples_done < 0 || samples_done > params->samples)
         return fail(PTG_ERR_INVALID_ARGUMENT, "samples_done must be in [0, samples]");
-    PTG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
-    if ((rc = fill_launch(ctx, params, A, grid)))
-        return rc;
-    if ((rc = ensure_acc(ctx, acc_elems_for(A), reinterpret_cast<hipStream_t>(stream))))
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true)))
         return rc;
     A.samps = samples_done;  // mean over the samples accumulated so far
     A.keep_acc = 1;
     A.resolve_row0 = 0;  // every row (the one-shot split tail does not apply here)
     A.acc = ctx->d_acc;
     A.out = d_slab;
-    return launch_resolve(A, reinterpret_cast<hipStream_t>(stream));
+    return launch_resolve(A, s);
 }
 
 int ptg_reset_accumulation_device(ptg_context *ctx, const ptg_params *params, void *stream)
@@ -3284,15 +2420,12 @@ int ptg_reset_accumulation_device(ptg_context *ctx, const ptg_params *params, vo
     int rc = check_params(params);
     if (rc)
         return rc;
-    PTG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
-    if ((rc = fill_launch(ctx, params, A, grid)))
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true)))
         return rc;
-    if ((rc = ensure_acc(ctx, acc_elems_for(A), reinterpret_cast<hipStream_t>(stream))))
-        return rc;
-    PTG_HIP(hipMemsetAsync(ctx->d_acc, 0, ctx->acc_elems * sizeof(unsigned long long),
-                           reinterpret_cast<hipStream_t>(stream)));
+    PTG_HIP(hipMemsetAsync(ctx->d_acc, 0, ctx->acc_elems * sizeof(unsigned long long), s));
     ctx->acc_dirty = false;
     return PTG_OK;
 }
@@ -3309,12 +2442,11 @@ int ptg_trace_samples_device(ptg_context *ctx, const ptg_params *params, const i
         return PTG_OK;
     if (params->flags & PTG_FLAG_REFERENCE_F64)
         return fail(PTG_ERR_UNSUPPORTED, "trace_samples probes the fp32 kernel");
-    PTG_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
-    if ((rc = fill_launch(ctx, params, A, grid)))
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/false)))
         return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     int blocks = (int)((n + kTraceBlock - 1) / kTraceBlock);
     const bool bvh = A.n > kLinearMax;
     if (A.exact_math)
@@ -3390,8 +2522,13 @@ int ptg_render(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *ca
     rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx);
     if (rc)
         return rc;
-    int32_t slab_rows = 0;
-    ptg_shard_rows(params->height, params->band_rows, params->shard_count, &slab_rows);
+    KArgs A;  // the frame's plan: the slab's geometry (and the reference-arithmetic mode's launch)
+    int grid = 0;
+    if ((rc = fill_launch(ctx->base, ctx->wave_slots, params, A, grid))) {
+        ptg_context_destroy(ctx);
+        return rc;
+    }
+    const int slab_rows = A.slab_rows;
     size_t slab_elems = (size_t)slab_rows * params->width * 3;
     // the reference-arithmetic mode keeps its doubles to the host image
     const bool f64 = (params->flags & PTG_FLAG_REFERENCE_F64) != 0;
@@ -3403,15 +2540,10 @@ int ptg_render(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *ca
         ptg_context_destroy(ctx);
         return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the image slab failed");
     }
-    if (f64) {
-        KArgs A;
-        int grid = 0;
-        rc = fill_launch(ctx, params, A, grid);
-        if (rc == PTG_OK)
-            rc = launch_ref64(ctx, A, static_cast<double *>(d_slab), nullptr, nullptr, nullptr);
-    } else {
+    if (f64)
+        rc = launch_ref64(ctx, A, static_cast<double *>(d_slab), nullptr, nullptr, nullptr);
+    else
         rc = ptg_render_device(ctx, params, static_cast<float *>(d_slab), nullptr, nullptr);
-    }
     if (rc == PTG_OK) {
         hipError_t e = hipDeviceSynchronize();
         if (e == hipSuccess)
@@ -3423,10 +2555,9 @@ int ptg_render(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *ca
     ptg_context_destroy(ctx);
     if (rc)
         return rc;
-    const int W = params->width, H = params->height, BR = params->band_rows;
+    const int W = params->width, H = params->height;
     for (int j = 0; j < slab_rows; ++j) {
-        int band = j / BR;
-        int r = (band * params->shard_count + params->shard_rank) * BR + (j - band * BR);
+        const int r = out_row_of(A, j);
         if (r >= H)
             continue;
         double *dst = image_rgb + (size_t)r * W * 3;

@@ -225,7 +225,9 @@ class MultiContext:
         return image
 
 
-KERNEL_SOURCES = ("ptg_render.hip", "pt_device.hpp", "bvh_build.hpp")
+# every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel)
+KERNEL_SOURCES = ("ptg_render.hip", "pt_device.hpp", "bvh_build.hpp", "kernel_args.hpp", "scene_prep.hpp",
+                  "launch_plan.hpp", "ptg_error.hpp")
 
 
 def kernel_source_hash() -> str:

@@ -545,7 +545,7 @@ static int g_bvar = 0;
 void po_set_mode_b_variant(int flags) { g_bvar = flags; }
 int po_get_mode_b_variant(void) { return g_bvar; }
 /* Anchored ("huge") form: R >= 1000, or R more than 16 times the camera's
- * distance to the surface (+1).  The kernel's host side: ptg_render.hip
+ * distance to the surface (+1).  The kernel's host side: kernel_args.hpp
  * is_huge. */
 static int is_huge_B(const po_sphere *sp, const po_camera *cam)
 {
@@ -669,7 +669,7 @@ typedef struct {
  * lies within max(diagonal, 1) of the box around the camera and the non-huge
  * spheres, it is the anchor instead (both are exact anchors; the kernel then
  * reads e_k, d_k instead of two dot products).  Returns k, or -1.  Same
- * choice as the kernel's host side (ptg_render.hip: choose_anchor). */
+ * choice as the kernel's host side (scene_prep.hpp: choose_anchor). */
 typedef struct { double lo[3], hi[3], diag; } boxB;
 
 static int choose_anchor_B(const po_sphere *sp, const po_camera *cam, const boxB *box, double P[3], double N[3])
@@ -726,14 +726,14 @@ static boxB scene_box_B(const po_sphere *s, int n, const po_camera *cam)
 static void trig_table_B(float *tab);
 
 /* Wall pairs (DESIGN.md "wall pairs"; the kernel's host side:
- * ptg_render.hip pair_walls): on each axis k the first axis-anchored huge
+ * scene_prep.hpp pair_walls): on each axis k the first axis-anchored huge
  * sphere with its centre on the + side of its anchor (N = -e_k) and the first
  * on the - side.  A ray whose origin has pair_lo <= o_k <= pair_hi (the
  * tangent planes x_k = a_minus, a_plus widened by 1e-4 max(1, diagonal)) tests
  * only the wall it moves toward (d_k >= 0: the + wall): each sphere lies
  * entirely beyond its tangent plane. */
 /* A wall may be paired / take part in box mode only if no ray origin can lie
- * genuinely inside it (the kernel's host side: ptg_render.hip wall_clear): not
+ * genuinely inside it (the kernel's host side: scene_prep.hpp wall_clear): not
  * dielectric, the camera on the room side by more than the margin. */
 static int wall_clear_B(const po_sphere *s, int i, int k, int plus_side, const po_camera *cam, const boxB *box)
 {
@@ -768,7 +768,7 @@ static void pair_walls_B(const po_sphere *s, int n, const po_camera *cam, const 
     }
 }
 
-/* Box mode (DESIGN.md "box mode"; the kernel's host side: ptg_render.hip
+/* Box mode (DESIGN.md "box mode"; the kernel's host side: scene_prep.hpp
  * box_mode_of): every axis-anchored wall is one of its axis's pair or the
  * only wall of its axis, some axis has a pair, no other huge sphere.  A
  * single wall's room bound (margin as pair_walls_B) goes into its own
@@ -859,7 +859,7 @@ static void prep_B(const po_sphere *s, int n, const po_camera *cam, sphB *out, c
         }
         b->mat = sp->material;
     }
-    /* linear scan order (the kernel's record order, ptg_render.hip
+    /* linear scan order (the kernel's record order, scene_prep.hpp
      * prepare_scan_order): x-, y-, z-axis-anchored huge spheres (each axis
      * led by its wall pair, + wall first), the other huge spheres, the small
      * ones; each group otherwise in index order */

@@ -8,7 +8,7 @@ surface -- the wall is hit there first -- so the rule holds; this is checked
 against the oracle with every sphere tested in index order (BV_FULL_SCAN: no
 pairs, no box mode).  What does break the premise is a path travelling
 inside a wall (a dielectric wall) or a camera inside the margin band: those
-walls are never paired (ptg_render.hip wall_clear, pt_oracle.c wall_clear_B).
+walls are never paired (scene_prep.hpp wall_clear, pt_oracle.c wall_clear_B).
 """
 import numpy as np
 
