@@ -1266,6 +1266,8 @@ __host__ __device__ __forceinline__ int out_row_of(const KArgs &A, int slab_row)
 // larger ones 2^30 -- the counting kernel reports such paths
 // (PTG_FLAG_COUNT_NONFINITE), none are expected
 __device__ __forceinline__ bool in_quant_range(float c) { return c >= 0.0f && c <= 0x1p30f; }
+// the clip quant() applies, as a value (the second moment squares it)
+__device__ __forceinline__ float quant_clip(float c) { return !(c >= 0.0f) ? 0.0f : (c > 0x1p30f ? 0x1p30f : c); }
 __device__ __forceinline__ unsigned long long quant(float c)
 {
     if (!(c >= 0.0f))
@@ -1285,11 +1287,17 @@ __device__ __forceinline__ unsigned long long quant(float c)
 // so all lanes stay busy until the pool is empty.  Path radiance is
 // accumulated exactly (u64) per slot in LDS and added to the global
 // accumulator once per unit.
-template <bool kCount, bool kBvh, bool kExact>
-__global__ __launch_bounds__(kBlockOf<kBvh>, PTG_MIN_WAVES_PER_EU) void render_kernel(KArgs A)
+//
+// The body of the render kernels.  kMoments (moments_kernel, progressive
+// passes with PTG_FLAG_MOMENTS): every finished path also adds
+// quant(cl(c) * cl(c)) of its components to a second per-slot LDS sum, added
+// to the second HBM accumulator acc2 (laid out like A.acc) at unit end.
+template <bool kCount, bool kBvh, bool kExact, bool kMoments>
+__device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *const acc2)
 {
     constexpr int kWaves = kBlockOf<kBvh> / 64;
     __shared__ unsigned long long lds_acc[kWaves][64 * 3];
+    __shared__ unsigned long long lds_acc2[kMoments ? kWaves : 1][kMoments ? 64 * 3 : 1];  // second moments
     __shared__ unsigned long long lds_key[kWaves][64];
     __shared__ uint32_t lds_pix[kWaves][64];  // slot -> x | sx << 20 | sy << 26
     // sphere records staged once per workgroup in LDS (uniform-address
@@ -1374,6 +1382,11 @@ __global__ __launch_bounds__(kBlockOf<kBvh>, PTG_MIN_WAVES_PER_EU) void render_k
     lds_acc[wv][lane] = 0ull;
     lds_acc[wv][lane + 64] = 0ull;
     lds_acc[wv][lane + 128] = 0ull;
+    if constexpr (kMoments) {
+        lds_acc2[wv][lane] = 0ull;
+        lds_acc2[wv][lane + 64] = 0ull;
+        lds_acc2[wv][lane + 128] = 0ull;
+    }
     if (lane < nv) {
         int px = x0 + (lane / A.lanes_per_pixel) * ps;
         int sub = lane % A.lanes_per_pixel;
@@ -1507,6 +1520,12 @@ __global__ __launch_bounds__(kBlockOf<kBvh>, PTG_MIN_WAVES_PER_EU) void render_k
         atomicAdd(&lds_acc[wv][sl], quant(ex));
         atomicAdd(&lds_acc[wv][sl + 64], quant(ey));
         atomicAdd(&lds_acc[wv][sl + 128], quant(ez));
+        if constexpr (kMoments) {
+            const float cx = quant_clip(ex), cy = quant_clip(ey), cz = quant_clip(ez);
+            atomicAdd(&lds_acc2[wv][sl], quant(cx * cx));
+            atomicAdd(&lds_acc2[wv][sl + 64], quant(cy * cy));
+            atomicAdd(&lds_acc2[wv][sl + 128], quant(cz * cz));
+        }
     };
     // A finished path parks its radiance (E, slot) in the lane's LDS record
     // lds_pre[wv][lane], which just gave up its prefetched ray; the quantise +
@@ -1862,8 +1881,32 @@ __global__ __launch_bounds__(kBlockOf<kBvh>, PTG_MIN_WAVES_PER_EU) void render_k
         if (vx) atomicAdd(g + 0, vx);
         if (vy) atomicAdd(g + 1, vy);
         if (vz) atomicAdd(g + 2, vz);
+        if constexpr (kMoments) {
+            unsigned long long *g2 = acc2 + (((size_t)row * A.W + px0) * A.lanes_per_pixel + ln) * 3;
+            const unsigned long long wx = lds_acc2[wv][ln], wy = lds_acc2[wv][ln + 64], wz = lds_acc2[wv][ln + 128];
+            if (wx) atomicAdd(g2 + 0, wx);
+            if (wy) atomicAdd(g2 + 1, wy);
+            if (wz) atomicAdd(g2 + 2, wz);
+        }
     }
     PTG_TRACE_END();
+}
+
+template <bool kCount, bool kBvh, bool kExact>
+__global__ __launch_bounds__(kBlockOf<kBvh>, PTG_MIN_WAVES_PER_EU) void render_kernel(KArgs A)
+{
+    render_unit<kCount, kBvh, kExact, false>(A, nullptr);
+}
+
+// Progressive passes with PTG_FLAG_MOMENTS (plan_single_level: every unit
+// accumulates in HBM, no in-wave or cooperative resolve).
+// The second LDS array leaves room for 6 waves per SIMD (8 without it): the
+// register budget follows.
+constexpr int kMomentsWavesPerEu = PTG_MIN_WAVES_PER_EU < 6 ? PTG_MIN_WAVES_PER_EU : 6;
+template <bool kBvh, bool kExact, bool kCount = false>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void moments_kernel(KArgs A, unsigned long long *acc2)
+{
+    render_unit<kCount, kBvh, kExact, true>(A, acc2);
 }
 
 // main.cpp:195-196: per pixel, the clamped sub-pixel means added with weight
@@ -1894,6 +1937,102 @@ __global__ __launch_bounds__(256) void resolve_kernel(KArgs A)
     out[0] = pix.x;
     out[1] = pix.y;
     out[2] = pix.z;
+}
+
+// ptg_noise_device (include/ptgpu.h "per-pixel noise estimates"): one thread
+// per slab pixel (grid-stride), from the exact sums A.acc (S1) and acc2 (S2)
+// after A.samps samples: the pixel value p as resolve_kernel computes it, per
+// channel the variance V of that value (every sub-pixel's variance of the
+// mean capped at 1/4: the image clamps the mean to [0, 1]) and the relative
+// standard error rho = sqrt(mean V) / max(mean p, floor); var / rho / stats
+// are optional.  stats: four integers, reduced per thread, per wave and per
+// workgroup (LDS), then one vector atomic per workgroup and value -- the
+// result does not depend on any order, and the grid is small enough
+// (ptg_noise_device: at most kNoiseBlocks workgroups) that the atomics on the
+// one cache line do not set the time (one per wave of a 1920x1080 frame:
+// 1.58 ms, against 0.22 ms without the stats).
+constexpr int kNoiseBlocks = 2048;  // 8 workgroups of 256 per CU on 256 CUs
+__global__ __launch_bounds__(256) void noise_kernel(KArgs A, const unsigned long long *__restrict__ acc2,
+                                                    double rel_error, double floor, float *__restrict__ var,
+                                                    float *__restrict__ rho_out, unsigned long long *stats)
+{
+    const long long total = (long long)A.slab_rows * A.W;
+    const long long stride = (long long)gridDim.x * 256;
+    unsigned over = 0u, cnt = 0u, rho_bits = 0u;
+    unsigned long long fixed = 0ull;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (out_row_of(A, (int)(i / A.W)) >= A.H)
+            continue;  // a slab row past the image
+        const unsigned long long *g1 = A.acc + (size_t)i * A.lanes_per_pixel * 3;
+        const unsigned long long *g2 = acc2 + (size_t)i * A.lanes_per_pixel * 3;
+        const double n = (double)A.samps;
+        f3 pix = mk3(0.0f, 0.0f, 0.0f);
+        double vs[3] = {0.0, 0.0, 0.0};
+        for (int j = 0; j < A.lanes_per_pixel; ++j) {
+            float m[3];
+            for (int c = 0; c < 3; ++c) {
+                const double m1 = ((double)g1[3 * j + c] * 0x1p-32) / n;
+                const double m2 = ((double)g2[3 * j + c] * 0x1p-32) / n;
+                const float mean = (float)m1;
+                m[c] = mean < 0.0f ? 0.0f : (1.0f < mean ? 1.0f : mean);
+                double v = m2 - m1 * m1;
+                v = (v > 0.0 ? v : 0.0) / (n - 1.0);
+                vs[c] += v < 0.25 ? v : 0.25;
+            }
+            pix = mk3(__builtin_fmaf(m[0], A.inv_sub2, pix.x), __builtin_fmaf(m[1], A.inv_sub2, pix.y),
+                      __builtin_fmaf(m[2], A.inv_sub2, pix.z));
+        }
+        const double w = (double)A.inv_sub2 * (double)A.inv_sub2;
+        const double V[3] = {w * vs[0], w * vs[1], w * vs[2]};
+        if (var) {
+            var[(size_t)i * 3 + 0] = (float)V[0];
+            var[(size_t)i * 3 + 1] = (float)V[1];
+            var[(size_t)i * 3 + 2] = (float)V[2];
+        }
+        const double sigma = __builtin_sqrt((V[0] + V[1] + V[2]) / 3.0);
+        const double mu = ((double)pix.x + (double)pix.y + (double)pix.z) / 3.0;
+        const float rho = (float)(sigma / (mu > floor ? mu : floor));
+        if (rho_out)
+            rho_out[i] = rho;
+        over += (double)rho > rel_error ? 1u : 0u;
+        fixed += (unsigned long long)((rho < 4096.0f ? rho : 4096.0f) * 0x1p20f);
+        const unsigned bits = __float_as_uint(rho);  // rho >= 0: the bit patterns order like the values
+        rho_bits = rho_bits > bits ? rho_bits : bits;
+        cnt += 1u;
+    }
+    if (!stats)
+        return;  // the whole grid
+    for (int off = 32; off > 0; off >>= 1) {  // every lane of the wave takes part
+        over += __shfl_xor(over, off, 64);
+        cnt += __shfl_xor(cnt, off, 64);
+        fixed += __shfl_xor(fixed, off, 64);
+        const unsigned other = __shfl_xor(rho_bits, off, 64);
+        rho_bits = rho_bits > other ? rho_bits : other;
+    }
+    __shared__ unsigned long long red[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long *r = red[threadIdx.x >> 6];
+        r[0] = over;
+        r[1] = fixed;
+        r[2] = rho_bits;
+        r[3] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t[4] = {0ull, 0ull, 0ull, 0ull};
+        for (int wv = 0; wv < 4; ++wv) {
+            t[0] += red[wv][0];
+            t[1] += red[wv][1];
+            t[2] = t[2] > red[wv][2] ? t[2] : red[wv][2];
+            t[3] += red[wv][3];
+        }
+        if (t[3]) {
+            atomicAdd(stats + 0, t[0]);
+            atomicAdd(stats + 1, t[1]);
+            atomicMax(stats + 2, t[2]);
+            atomicAdd(stats + 3, t[3]);
+        }
+    }
 }
 
 // Parity probe: one path per record {x, y, sx, sy, sample}.
@@ -1993,6 +2132,11 @@ struct ptg_context {
     KArgs base;  // camera + scene fields filled
     ptg_sphere *d_sph64;  // the scene as given (PTG_FLAG_REFERENCE_F64)
     ptg_camera cam64;
+    // PTG_FLAG_MOMENTS: exact per-sub-pixel sums of squares, laid out like d_acc; allocated on first use
+    unsigned long long *d_acc2;
+    size_t acc2_elems;
+    bool moments_pass;  // a pass since the last reset added to d_acc2 ...
+    bool plain_pass;    // ... or ran without the flag (d_acc2 then lacks its samples: no noise estimate)
 };
 
 namespace {
@@ -2199,6 +2343,8 @@ int ptg_context_destroy(ptg_context *ctx)
         (void)hipFree(ctx->d_bvh);
     if (ctx->d_acc)
         (void)hipFree(ctx->d_acc);
+    if (ctx->d_acc2)
+        (void)hipFree(ctx->d_acc2);
     if (ctx->d_sph64)
         (void)hipFree(ctx->d_sph64);
     delete ctx;
@@ -2208,6 +2354,17 @@ int ptg_context_destroy(ptg_context *ctx)
 }  // extern "C"
 
 namespace {
+
+size_t acc_elems_for(const KArgs &A) { return (size_t)A.slab_rows * A.W * A.lanes_per_pixel * 3; }
+
+// the second accumulator zero and no pass on record
+int forget_moments(ptg_context *ctx, hipStream_t stream)
+{
+    if (ctx->d_acc2 && ctx->moments_pass)  // (only such passes write to it)
+        PTG_HIP(hipMemsetAsync(ctx->d_acc2, 0, ctx->acc2_elems * sizeof(unsigned long long), stream));
+    ctx->moments_pass = ctx->plain_pass = false;
+    return PTG_OK;
+}
 
 // exact accumulator: allocated (zeroed) on first use at a size; resolve_kernel
 // keeps it zero between one-shot frames.  The zeroing is queued on the launch
@@ -2227,10 +2384,49 @@ int ensure_acc(ptg_context *ctx, size_t need, hipStream_t stream)
     PTG_HIP(hipMemsetAsync(ctx->d_acc, 0, need * sizeof(unsigned long long), stream));
     ctx->acc_elems = need;
     ctx->acc_dirty = false;  // (a progressive frame in the old buffer is lost: reset before reuse)
+    return forget_moments(ctx, stream);
+}
+
+// PTG_FLAG_MOMENTS passes: the second accumulator at the first one's size
+// (ensure_acc first), zeroed on allocation like it
+int ensure_acc2(ptg_context *ctx, hipStream_t stream)
+{
+    if (ctx->acc_elems <= ctx->acc2_elems)
+        return PTG_OK;
+    if (ctx->d_acc2)
+        PTG_HIP(hipFree(ctx->d_acc2));
+    ctx->d_acc2 = nullptr;
+    ctx->acc2_elems = 0;
+    if (hipMalloc(&ctx->d_acc2, ctx->acc_elems * sizeof(unsigned long long)) != hipSuccess)
+        return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the second-moment accumulator failed");
+    PTG_HIP(hipMemsetAsync(ctx->d_acc2, 0, ctx->acc_elems * sizeof(unsigned long long), stream));
+    ctx->acc2_elems = ctx->acc_elems;
     return PTG_OK;
 }
 
-size_t acc_elems_for(const KArgs &A) { return (size_t)A.slab_rows * A.W * A.lanes_per_pixel * 3; }
+// Both accumulators zero, no progressive frame in them (reset; a one-shot
+// frame that needs the first accumulator after progressive passes)
+int clear_accumulation(ptg_context *ctx, hipStream_t stream)
+{
+    if (ctx->d_acc)
+        PTG_HIP(hipMemsetAsync(ctx->d_acc, 0, ctx->acc_elems * sizeof(unsigned long long), stream));
+    ctx->acc_dirty = false;
+    return forget_moments(ctx, stream);
+}
+
+// ptg_noise_device / ptg_read_moments_device: the second accumulator holds
+// the squares of exactly the samples the first one holds
+int check_moments(const ptg_context *ctx, const KArgs &A, const char *who)
+{
+    if (!ctx->moments_pass)
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": no PTG_FLAG_MOMENTS pass since the last reset");
+    if (ctx->plain_pass)
+        return fail(PTG_ERR_INVALID_ARGUMENT,
+                    std::string(who) + ": a pass since the last reset ran without PTG_FLAG_MOMENTS");
+    if (!ctx->d_acc2 || ctx->acc2_elems < acc_elems_for(A) || ctx->acc_elems < acc_elems_for(A))
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": the passes were of a smaller frame");
+    return PTG_OK;
+}
 
 // The device entry points' common start, after their argument checks: the
 // context's device current and the launch plan for samples [s_begin, s_end);
@@ -2243,15 +2439,23 @@ int begin_launch(ptg_context *ctx, const ptg_params *p, KArgs &A, int &grid, hip
     return rc || !with_acc ? rc : ensure_acc(ctx, acc_elems_for(A), s);
 }
 
-int launch_render(const KArgs &A, int grid, bool count, hipStream_t s)
+int launch_render(const KArgs &A, int grid, bool count, hipStream_t s, unsigned long long *acc2 = nullptr)
 {
     if (grid <= 0)
         return PTG_OK;
     const bool bvh = A.n > kLinearMax;
     const size_t lds = bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
     // the exact mode's sin/cos table has its own LDS (render_kernel)
-    const int sel = (count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0);
+    const int sel = (acc2 ? 8 : 0) | (count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0);
     switch (sel) {
+    case 8: moments_kernel<false, false, false><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 9: moments_kernel<false, true, false><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 10: moments_kernel<true, false, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 11: moments_kernel<true, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 12: moments_kernel<false, false, true><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 13: moments_kernel<false, true, true><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 14: moments_kernel<true, false, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 15: moments_kernel<true, true, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
     case 0: render_kernel<false, false, false><<<grid, kBlock, lds, s>>>(A); break;
     case 1: render_kernel<false, false, true><<<grid, kBlock, lds, s>>>(A); break;
     case 2: render_kernel<false, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A); break;
@@ -2338,8 +2542,8 @@ int ptg_render_device(ptg_context *ctx, const ptg_params *params, float *d_slab,
     if (resolve && ctx->acc_dirty) {
         // progressive sums left by accumulate / keep_acc resolve: a one-shot
         // frame starts from zero (its resolve leaves the buffer zero again)
-        PTG_HIP(hipMemsetAsync(ctx->d_acc, 0, ctx->acc_elems * sizeof(unsigned long long), s));
-        ctx->acc_dirty = false;
+        if ((rc = clear_accumulation(ctx, s)))
+            return rc;
     }
     if ((rc = launch_render(A, grid, d_segments != nullptr, s)))
         return rc;
@@ -2385,10 +2589,15 @@ int ptg_accumulate_device(ptg_context *ctx, const ptg_params *params, int32_t sa
     if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true, sample_begin, sample_end,
                            /*accumulate_only=*/true)))
         return rc;
+    const bool moments = (params->flags & PTG_FLAG_MOMENTS) != 0;
+    if (moments && (rc = ensure_acc2(ctx, s)))
+        return rc;
     A.acc = ctx->d_acc;
     A.segments = d_segments;
     ctx->acc_dirty = true;
-    return launch_render(A, grid, d_segments != nullptr, s);
+    if (grid > 0)  // (an empty pass adds no samples to either accumulator)
+        (moments ? ctx->moments_pass : ctx->plain_pass) = true;
+    return launch_render(A, grid, d_segments != nullptr, s, moments ? ctx->d_acc2 : nullptr);
 }
 
 int ptg_resolve_device(ptg_context *ctx, const ptg_params *params, int32_t samples_done, float *d_slab, void *stream)
@@ -2425,8 +2634,81 @@ int ptg_reset_accumulation_device(ptg_context *ctx, const ptg_params *params, vo
     int grid = 0;
     if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true)))
         return rc;
-    PTG_HIP(hipMemsetAsync(ctx->d_acc, 0, ctx->acc_elems * sizeof(unsigned long long), s));
-    ctx->acc_dirty = false;
+    return clear_accumulation(ctx, s);
+}
+
+int ptg_noise_device(ptg_context *ctx, const ptg_params *params, int32_t samples_done, double rel_error, double floor,
+                     float *d_var, float *d_rho, unsigned long long *d_stats, void *stream)
+{
+    if (!ctx)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (samples_done < 2 || samples_done > params->samples)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "noise: samples_done must be in [2, samples]");
+    if (!(floor > 0.0) || !(rel_error >= 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "noise: floor must be > 0 and rel_error >= 0");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    int grid = 0;
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true)) || (rc = check_moments(ctx, A, "noise")))
+        return rc;
+    A.samps = samples_done;
+    A.acc = ctx->d_acc;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    if (pixels <= 0 || (!d_var && !d_rho && !d_stats))
+        return PTG_OK;
+    const long long blocks = (pixels + 255) / 256;  // the kernel strides over the rest
+    noise_kernel<<<(unsigned)(blocks < kNoiseBlocks ? blocks : kNoiseBlocks), 256, 0, s>>>(
+        A, ctx->d_acc2, rel_error, floor, d_var, d_rho, d_stats);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_read_moments_device(ptg_context *ctx, const ptg_params *params, unsigned long long *d_sum,
+                            unsigned long long *d_sumsq, void *stream)
+{
+    if (!ctx)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    int grid = 0;
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/true)))
+        return rc;
+    const size_t bytes = acc_elems_for(A) * sizeof(unsigned long long);
+    if (d_sumsq) {
+        if ((rc = check_moments(ctx, A, "read_moments")))
+            return rc;
+        PTG_HIP(hipMemcpyAsync(d_sumsq, ctx->d_acc2, bytes, hipMemcpyDeviceToDevice, s));
+    }
+    if (d_sum)
+        PTG_HIP(hipMemcpyAsync(d_sum, ctx->d_acc, bytes, hipMemcpyDeviceToDevice, s));
+    return PTG_OK;
+}
+
+int ptg_noise_schedule(int32_t min_samples, int32_t samples, int32_t *ends, int32_t cap, int32_t *n)
+{
+    if (!ends || !n)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "noise_schedule: NULL argument");
+    *n = 0;
+    if (min_samples < 2 || samples < 2)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "noise_schedule: min_samples and samples must be >= 2 (a variance "
+                                              "needs two samples)");
+    int32_t k = 0;
+    for (int64_t e = min_samples; e < samples; e *= 2, ++k)
+        if (k < cap)
+            ends[k] = (int32_t)e;
+    if (k < cap)
+        ends[k] = samples;
+    ++k;
+    if (k > cap)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "noise_schedule: " + std::to_string(k) + " passes, room for " +
+                                                  std::to_string(cap));
+    *n = k;
     return PTG_OK;
 }
 
@@ -2566,6 +2848,97 @@ int ptg_render(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *ca
             dst[i] = dst[i] + (f64 ? reinterpret_cast<const double *>(host.data())[off + i]
                                    : (double)reinterpret_cast<const float *>(host.data())[off + i]);
     }
+    return PTG_OK;
+}
+
+int ptg_render_to_noise(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
+                        int device, const ptg_noise_target *target, double *image_rgb, ptg_noise_report *report)
+{
+    if (!image_rgb || !target)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: NULL image or target");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (!(target->floor > 0.0) || !(target->rel_error >= 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: floor must be > 0 and rel_error >= 0");
+    if (!(target->max_fraction >= 0.0 && target->max_fraction < 1.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: max_fraction must be in [0, 1)");
+    if (params->shard_count != 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: shard_count must be 1 (one device decides for "
+                                              "the whole frame)");
+    if (params->flags & PTG_FLAG_REFERENCE_F64)
+        return fail(PTG_ERR_UNSUPPORTED, "render_to_noise: progressive passes are fp32 only");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    if ((rc = ptg_noise_schedule(target->min_samples, params->samples, ends, PTG_NOISE_MAX_PASSES, &n_ends)))
+        return rc;
+    ptg_noise_report rep{};
+    ptg_context *ctx = nullptr;
+    if ((rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx)))
+        return rc;
+    ptg_params p = *params;
+    p.flags |= PTG_FLAG_MOMENTS;
+    const int W = p.width, H = p.height;
+    const int slab_rows = shard_slab_rows(H, p.band_rows, 1);
+    const size_t slab_elems = (size_t)slab_rows * W * 3;
+    std::vector<float> host(slab_elems);
+    float *d_slab = nullptr;
+    unsigned long long *d_stats = nullptr;
+    // everything on the null stream, in order; each check's 32 bytes copied back synchronously
+    auto run = [&]() -> int {
+        int r;
+        if (hipMalloc(&d_slab, slab_elems * sizeof(float)) != hipSuccess ||
+            hipMalloc(&d_stats, 4 * sizeof(unsigned long long)) != hipSuccess)
+            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the image slab failed");
+        if ((r = ptg_reset_accumulation_device(ctx, &p, nullptr)))
+            return r;
+        int32_t done = 0;
+        for (int k = 0; k < n_ends; ++k) {
+            unsigned long long st[4] = {0, 0, 0, 0};
+            PTG_HIP(hipMemsetAsync(d_stats, 0, sizeof(st), nullptr));
+            if ((r = ptg_accumulate_device(ctx, &p, done, ends[k], nullptr, nullptr)))
+                return r;
+            done = ends[k];
+            if ((r = ptg_noise_device(ctx, &p, done, target->rel_error, target->floor, nullptr, nullptr, d_stats,
+                                      nullptr)))
+                return r;
+            PTG_HIP(hipMemcpy(st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
+            rep.samples_done = done;
+            rep.passes = k + 1;
+            rep.pixels = st[3];
+            rep.pixels_over = st[0];
+            rep.pass_samples[k] = done;
+            rep.pass_over[k] = st[0];
+            const uint32_t max_bits = (uint32_t)st[2];
+            float max_rho;
+            std::memcpy(&max_rho, &max_bits, sizeof(max_rho));
+            rep.max_rho = (double)max_rho;
+            rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
+            rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
+            if (rep.converged)
+                break;
+        }
+        if ((r = ptg_resolve_device(ctx, &p, done, d_slab, nullptr)))
+            return r;
+        PTG_HIP(hipMemcpy(host.data(), d_slab, slab_elems * sizeof(float), hipMemcpyDeviceToHost));
+        return PTG_OK;
+    };
+    rc = run();
+    if (d_slab)
+        (void)hipFree(d_slab);
+    if (d_stats)
+        (void)hipFree(d_stats);
+    ptg_context_destroy(ctx);
+    if (rc)
+        return rc;
+    for (int j = 0; j < slab_rows; ++j) {  // shard_count 1: slab row j is output row j
+        if (j >= H)
+            continue;
+        double *dst = image_rgb + (size_t)j * W * 3;
+        for (int i = 0; i < W * 3; ++i)  // main.cpp:196: image[row] += ...
+            dst[i] = dst[i] + (double)host[(size_t)j * W * 3 + i];
+    }
+    if (report)
+        *report = rep;
     return PTG_OK;
 }
 

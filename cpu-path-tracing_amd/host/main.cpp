@@ -6,6 +6,7 @@
 //   pt_render_gpu [--spp N] [--scene NAME|FILE] [--width W] [--height H] [--seed S]
 //                 [--devices 0,1,...] [--out FILE] [--format p3|p6]
 //                 [--save-scene FILE] [--dump-json FILE] [--no-render] [--exact-math]
+//                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]]
 //
 //   spp      total samples per pixel (main.cpp:206: divided by the 4 sub-pixels), default 4
 //   scene    box_mirror (the reference binary's scene, main.cpp:25,208) | box | simple |
@@ -18,6 +19,12 @@
 //            (main.cpp:240-247, utils.cpp:11-16)
 //   --exact-math  the kernel's exact arithmetic (PTG_FLAG_EXACT_MATH): the image equals
 //            the CPU oracle's bit for bit (default: the GPU's fast transcendentals)
+//   --noise-target R  render until converged (ptg_render_to_noise): passes of min-spp,
+//            2 min-spp, 4 min-spp, ... samples per pixel (default 64), at most --spp; stop
+//            when at most the fraction Q (default 0.01) of the pixels has a relative
+//            standard error above R, relative to max(pixel mean, F) (default 0.01).  The
+//            image equals a plain run's at the spp the "noise:" line on stderr reports.
+//            One device only (a --devices list of several: exit status 2).
 //   --save-scene / --dump-json write the scene (scene file) / the scene and the
 //            camera::with_config result (JSON, 17 digits) and need no GPU with --no-render
 #include <chrono>
@@ -108,6 +115,11 @@ int main(int argc, char *argv[])
     std::uint64_t seed = pt::gpu::default_seed;
     bool render = true;
     int flags = 0;
+    bool to_noise = false;
+    int min_spp = 64;
+    ptg_noise_target target{};
+    target.floor = 0.01;
+    target.max_fraction = 0.01;
     if (argc > 1 && std::strncmp(argv[1], "--", 2) != 0) {  // the positional form
         spp = std::atoi(argv[1]);
         if (argc > 2)
@@ -152,6 +164,15 @@ int main(int argc, char *argv[])
                 render = false;
             else if (a == "--exact-math")
                 flags |= PTG_FLAG_EXACT_MATH;
+            else if (a == "--noise-target") {
+                to_noise = true;
+                target.rel_error = std::atof(val().c_str());
+            } else if (a == "--noise-floor")
+                target.floor = std::atof(val().c_str());
+            else if (a == "--noise-fraction")
+                target.max_fraction = std::atof(val().c_str());
+            else if (a == "--min-spp")
+                min_spp = std::atoi(val().c_str());
             else {
                 std::fprintf(stderr, "unknown option %s\n", a.c_str());
                 return 2;
@@ -185,7 +206,26 @@ int main(int argc, char *argv[])
     int const nd = static_cast<int>(devs.size());
     auto const t0 = std::chrono::steady_clock::now();
     int rc = PTG_OK;
-    if (nd == 1 && devs[0] < 0) {  // main.cpp:214-236 replaced by one call
+    int samps_done = samps;
+    if (to_noise) {  // render until converged: --spp is the most it takes
+        if (nd != 1) {
+            std::fprintf(stderr, "--noise-target renders on one device\n");
+            return 2;
+        }
+        target.min_samples = min_spp / (num_subpixels * num_subpixels);
+        ptg_noise_report rep{};
+        rc = pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep, num_subpixels,
+                                            seed, devs[0], flags);
+        if (rc == PTG_OK) {
+            samps_done = rep.samples_done;
+            std::fprintf(stderr,
+                         "noise: stopped at %d spp after %d passes, %llu/%llu pixels above %g, max %g, mean %g, "
+                         "converged %d\n",
+                         samps_done * num_subpixels * num_subpixels, rep.passes,
+                         static_cast<unsigned long long>(rep.pixels_over), static_cast<unsigned long long>(rep.pixels),
+                         target.rel_error, rep.max_rho, rep.mean_rho, rep.converged);
+        }
+    } else if (nd == 1 && devs[0] < 0) {  // main.cpp:214-236 replaced by one call
         rc = pt::gpu::render_image(some_scene, cam, image, width, height, samps, num_subpixels, seed, -1, flags);
     } else {  // several GPUs of this process: shards + one RCCL gather
         ptg_params p{};
@@ -209,8 +249,8 @@ int main(int argc, char *argv[])
     }
     double const secs = std::chrono::duration<double>(t1 - t0).count();
     std::fprintf(stderr, "Rendered %s %dx%d at %d spp on %d device(s) in %.3f s (%.1f Msamples/s incl. setup + copies)\n",
-                 scene_name.c_str(), width, height, samps * num_subpixels * num_subpixels, nd, secs,
-                 double(width) * height * samps * num_subpixels * num_subpixels / secs / 1e6);
+                 scene_name.c_str(), width, height, samps_done * num_subpixels * num_subpixels, nd, secs,
+                 double(width) * height * samps_done * num_subpixels * num_subpixels / secs / 1e6);
 
     std::ofstream g{out, std::ios::binary};
     if (format == "p6") {

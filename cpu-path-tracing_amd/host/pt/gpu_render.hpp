@@ -60,5 +60,30 @@ inline int render_image(scene const &scn, camera const &cam, std::vector<vec3> &
                       reinterpret_cast<double *>(image.data()));
 }
 
+// render_image that stops as soon as the noise target is met (ptg_render_to_noise):
+// `samps` is the most it takes; the image equals render_image's at samps =
+// report.samples_done.  target: {rel_error, floor, max_fraction, min_samples}.
+inline int render_image_to_noise(scene const &scn, camera const &cam, std::vector<vec3> &image, int width, int height,
+                                 int samps, ptg_noise_target const &target, ptg_noise_report &report,
+                                 int num_subpixels = 2, std::uint64_t seed = default_seed, int device = -1,
+                                 int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return ptg_render_to_noise(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                               reinterpret_cast<ptg_camera const *>(&cam), &p, device, &target,
+                               reinterpret_cast<double *>(image.data()), &report);
+}
+
 }  // namespace gpu
 }  // namespace pt

@@ -23,6 +23,7 @@ EXPORTS = (
     "ptg_multi_reset_accumulation", "ptg_multi_accumulate", "ptg_multi_resolve", "ptg_multi_frame_device",
     "ptg_multi_frame_timing", "ptg_multi_image", "ptg_math_probe_device", "ptg_multi_comm_info",
     "ptg_device_pci_bus_id", "ptg_launch_info",
+    "ptg_noise_device", "ptg_read_moments_device", "ptg_noise_schedule", "ptg_render_to_noise",
 )
 
 
@@ -38,6 +39,23 @@ class Params(C.Structure):  # ptg_params
 
 
 assert C.sizeof(Params) == 48
+
+NOISE_MAX_PASSES = 32  # include/ptgpu.h PTG_NOISE_MAX_PASSES
+
+
+class NoiseTarget(C.Structure):  # ptg_noise_target
+    _fields_ = [("rel_error", C.c_double), ("floor", C.c_double), ("max_fraction", C.c_double),
+                ("min_samples", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class NoiseReport(C.Structure):  # ptg_noise_report
+    _fields_ = [("samples_done", C.c_int32), ("passes", C.c_int32), ("converged", C.c_int32),
+                ("reserved_", C.c_int32), ("pixels", C.c_uint64), ("pixels_over", C.c_uint64),
+                ("max_rho", C.c_double), ("mean_rho", C.c_double), ("pass_samples", C.c_int32 * NOISE_MAX_PASSES),
+                ("pass_over", C.c_uint64 * NOISE_MAX_PASSES)]
+
+
+assert C.sizeof(NoiseTarget) == 32 and C.sizeof(NoiseReport) == 48 + 12 * NOISE_MAX_PASSES
 
 _lib = None
 
@@ -81,6 +99,11 @@ def lib():
             "ptg_multi_comm_info": (I, [P, P, P, P, I]),
             "ptg_device_pci_bus_id": (I, [I, C.c_char_p, I]),
             "ptg_launch_info": (I, [P, C.POINTER(Params), P, I]),
+            "ptg_noise_device": (I, [P, C.POINTER(Params), C.c_int32, C.c_double, C.c_double, P, P, P, P]),
+            "ptg_read_moments_device": (I, [P, C.POINTER(Params), P, P, P]),
+            "ptg_noise_schedule": (I, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+            "ptg_render_to_noise": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(NoiseTarget), P,
+                                        C.POINTER(NoiseReport)]),
             "ptg_multi_inject_gather_fault_": (I, [P, I]),
             # internal (tests): n shards on one device, gathered by device copies
             "ptg_multi_create_local_": (I, [P, C.c_size_t, P, I, I, C.POINTER(C.c_void_p)]),

@@ -19,7 +19,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from ._abi import Params, check, lib
+from ._abi import NOISE_MAX_PASSES, NoiseReport, NoiseTarget, Params, check, lib
 from .scene import CAMERA_DT, SPHERE_DT, camera, scene
 
 DEFAULT_SEED = 0x5EED0001
@@ -48,6 +48,7 @@ FLAG_COUNT_TESTS = 1  # include/ptgpu.h PTG_FLAG_COUNT_TESTS
 FLAG_COUNT_NONFINITE = 2  # include/ptgpu.h PTG_FLAG_COUNT_NONFINITE (4 counters)
 FLAG_REFERENCE_F64 = 4  # include/ptgpu.h PTG_FLAG_REFERENCE_F64: the reference's double arithmetic (parity mode)
 FLAG_EXACT_MATH = 8  # include/ptgpu.h PTG_FLAG_EXACT_MATH: exact sequences, bit for bit the oracle's Mode B
+FLAG_MOMENTS = 16  # include/ptgpu.h PTG_FLAG_MOMENTS: progressive passes also sum second moments (Context.noise)
 
 
 def _n_counters(flags: int) -> int:
@@ -101,6 +102,41 @@ def render(scn, cam, image: np.ndarray, width: int, height: int, samples: int, n
     check(lib().ptg_render(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p), C.byref(p),
                            int(device), img.ctypes.data_as(C.c_void_p)), "ptg_render")
     return image
+
+
+def noise_schedule(min_samples: int, samples: int) -> list:
+    """ptg_noise_schedule (host only): the pass ends min_samples, 2 min_samples,
+    ... of a render-until-converged frame; the last one is `samples`."""
+    ends = (C.c_int32 * NOISE_MAX_PASSES)()
+    n = C.c_int32(0)
+    check(lib().ptg_noise_schedule(int(min_samples), int(samples), ends, NOISE_MAX_PASSES, C.byref(n)),
+          "ptg_noise_schedule")
+    return list(ends[:n.value])
+
+
+def render_to_noise(scn, cam, image: np.ndarray, width: int, height: int, samples: int, rel_error: float,
+                    floor: float = 0.01, max_fraction: float = 0.01, min_samples: int = 16, num_subpixels: int = 2,
+                    seed: int = DEFAULT_SEED, device: int = -1, flags: int = 0) -> dict:
+    """ptg_render_to_noise: render() that stops at the first of the passes
+    noise_schedule(min_samples, samples) after which at most max_fraction of
+    the pixels has a relative standard error above rel_error (`floor`: the
+    least pixel mean the error is taken relative to).  The image equals
+    render()'s at samples = the returned samples_done bit for bit.  Returns
+    the report: samples_done, passes, converged, pixels, pixels_over, max_rho,
+    mean_rho, pass_samples, pass_over."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    if image.dtype != np.float64 or not image.flags["C_CONTIGUOUS"] or image.size != width * height * 3:
+        raise ValueError("image must be a C-contiguous float64 array of width*height*3 values")
+    p = make_params(width, height, samples, num_subpixels, seed, flags=flags)
+    target = NoiseTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), 0)
+    rep = NoiseReport()
+    check(lib().ptg_render_to_noise(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
+                                    C.byref(p), int(device), C.byref(target), image.ctypes.data_as(C.c_void_p),
+                                    C.byref(rep)), "ptg_render_to_noise")
+    return {"samples_done": rep.samples_done, "passes": rep.passes, "converged": rep.converged,
+            "pixels": rep.pixels, "pixels_over": rep.pixels_over, "max_rho": rep.max_rho, "mean_rho": rep.mean_rho,
+            "pass_samples": list(rep.pass_samples[:rep.passes]), "pass_over": list(rep.pass_over[:rep.passes])}
 
 
 def render_multi(scn, cam, image: np.ndarray, width: int, height: int, samples: int, devices,
@@ -360,6 +396,42 @@ class Context:
         s = self._stream(stream)
         check(lib().ptg_resolve_device(self._h, C.byref(params), int(samples_done), C.c_void_p(out.data_ptr()),
                                        C.c_void_p(s)), "ptg_resolve_device")
+
+    # ---- per-pixel noise estimates (ptg_noise_device, after FLAG_MOMENTS passes)
+    def noise(self, params: Params, samples_done: int, rel_error: float, floor: float, var=None, rho=None,
+              stats=None, stream=None) -> None:
+        """Noise of the samples accumulated so far: `var` (float32, slab
+        rows*W*3: variance of every pixel value), `rho` (float32, slab rows*W:
+        relative standard error) and `stats` (int64 [4], zeroed by the caller:
+        += pixels with rho > rel_error, += fixed-point sum of rho, max of
+        rho's bits, += pixels), each optional."""
+        import torch
+        pixels = shard_rows(params.height, params.band_rows, params.shard_count) * params.width
+        if var is not None:
+            self._check(var, torch.float32, pixels * 3)
+        if rho is not None:
+            self._check(rho, torch.float32, pixels)
+        if stats is not None:
+            self._check(stats, torch.int64, 4)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        s = self._stream(stream)
+        check(lib().ptg_noise_device(self._h, C.byref(params), int(samples_done), float(rel_error), float(floor),
+                                     ptr(var), ptr(rho), ptr(stats), C.c_void_p(s)), "ptg_noise_device")
+
+    def read_moments(self, params: Params, sums=None, sumsq=None, stream=None) -> None:
+        """The raw exact sums (int64 tensors of slab rows*W*nsub^2*3 values,
+        index ((row*W + x)*nsub^2 + sub)*3 + c): `sums` of q(c), `sumsq` of
+        q(cl(c)^2) (after FLAG_MOMENTS passes only)."""
+        import torch
+        n = (shard_rows(params.height, params.band_rows, params.shard_count) * params.width
+             * params.num_subpixels ** 2 * 3)
+        for t in (sums, sumsq):
+            if t is not None:
+                self._check(t, torch.int64, n)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        s = self._stream(stream)
+        check(lib().ptg_read_moments_device(self._h, C.byref(params), ptr(sums), ptr(sumsq), C.c_void_p(s)),
+              "ptg_read_moments_device")
 
     def trace_samples(self, coords, params: Params):
         """Parity probe: radiance + segment count of individual paths

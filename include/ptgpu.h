@@ -122,6 +122,12 @@ typedef struct ptg_params {
  * modes").  Either way a frame does not depend on sharding, work-unit sizes,
  * progressive passes or the GPU count. */
 #define PTG_FLAG_EXACT_MATH 8
+/* PTG_FLAG_MOMENTS: a progressive pass (ptg_accumulate_device) also sums the
+ * second moment of every path exactly: per (pixel, sub-pixel, channel)
+ * S2 += q(cl(c) * cl(c)), cl the clip of q (NaN and negative to 0, above 2^30
+ * to 2^30), the product one fp32 multiply -- the input of ptg_noise_device.
+ * The image is not affected.  No effect outside ptg_accumulate_device. */
+#define PTG_FLAG_MOMENTS 16
 
 typedef struct ptg_context ptg_context;
 
@@ -246,6 +252,79 @@ int ptg_accumulate_device(ptg_context *ctx, const ptg_params *params, int32_t sa
                           unsigned long long *d_segments, void *stream);
 int ptg_resolve_device(ptg_context *ctx, const ptg_params *params, int32_t samples_done, float *d_slab,
                        void *stream);
+
+/* ---- per-pixel noise estimates (DESIGN.md "noise estimates") ----------
+ * Passes with PTG_FLAG_MOMENTS keep, beside the exact sums S1 of q(c), the
+ * exact sums S2 of q(cl(c)^2) in a second accumulator the context owns
+ * (allocated on first use, cleared by ptg_reset_accumulation_device).  After
+ * n = samples_done >= 2 samples, all in double and in (sy, sx) order:
+ *   m1 = S1 2^-32 / n, m2 = S2 2^-32 / n,
+ *   v = max(0, m2 - m1 m1) / (n - 1)          variance of the sub-pixel mean
+ *   V_c = inv_sub2^2 sum_sub min(v, 1/4)      inv_sub2 = (float)1 / nsub^2; the
+ *        image clamps every sub-pixel mean to [0, 1], whose variance is at
+ *        most 1/4
+ *   p_c = the pixel value of ptg_resolve_device
+ *   rho = (float)(sqrt((V_r + V_g + V_b) / 3) / max((p_r + p_g + p_b) / 3, floor))
+ * d_var (slab_rows * width * 3 floats: (float)V_c), d_rho (slab_rows * width
+ * floats: the relative standard error rho) and d_stats are each optional;
+ * slab rows past the image are left untouched.  d_stats: 4 uint64 the caller
+ * zeroes, [0] += pixels with rho > rel_error, [1] += trunc(min(rho, 4096) *
+ * 2^20), [2] = max(the bits of rho), [3] += pixels visited -- integers, so
+ * deterministic, and the stats of shards add (max for [2]).
+ * PTG_ERR_INVALID_ARGUMENT when samples_done < 2 or > samples, floor <= 0,
+ * rel_error < 0, no PTG_FLAG_MOMENTS pass has run since the last reset, or a
+ * pass since the last reset ran without the flag.  Asynchronous on stream. */
+int ptg_noise_device(ptg_context *ctx, const ptg_params *params, int32_t samples_done, double rel_error,
+                     double floor, float *d_var, float *d_rho, unsigned long long *d_stats, void *stream);
+
+/* The raw sums of the slab, copied to d_sum (S1) and d_sumsq (S2), each
+ * optional: slab_rows * width * num_subpixels^2 * 3 uint64, index
+ * ((slab_row * width + x) * num_subpixels^2 + sy * num_subpixels + sx) * 3 + c.
+ * Sums of frames with different seeds may be added by the caller.  d_sumsq
+ * under the conditions of ptg_noise_device.  Asynchronous on stream. */
+int ptg_read_moments_device(ptg_context *ctx, const ptg_params *params, unsigned long long *d_sum,
+                            unsigned long long *d_sumsq, void *stream);
+
+/* Host only: the pass ends of a render-until-converged frame: min_samples,
+ * 2 min_samples, 4 min_samples, ... below samples, then samples (so the last
+ * entry is samples; min_samples > samples gives the one entry samples).
+ * min_samples >= 2, samples >= 2.  *n receives the count; cap is the room in
+ * ends (PTG_ERR_INVALID_ARGUMENT when too small; PTG_NOISE_MAX_PASSES always
+ * suffices). */
+#define PTG_NOISE_MAX_PASSES 32
+int ptg_noise_schedule(int32_t min_samples, int32_t samples, int32_t *ends, int32_t cap, int32_t *n);
+
+typedef struct ptg_noise_target {
+    double rel_error;    /* a pixel is over the target when rho > rel_error (>= 0) */
+    double floor;        /* rho's denominator is max(pixel mean, floor) (> 0) */
+    double max_fraction; /* stop when at most this fraction of the pixels is over; in [0, 1) */
+    int32_t min_samples; /* first check after this many samples per sub-pixel (>= 2) */
+    int32_t reserved_;
+} ptg_noise_target;
+
+typedef struct ptg_noise_report {
+    int32_t samples_done; /* samples per sub-pixel in the image */
+    int32_t passes;
+    int32_t converged;    /* the last check met the target */
+    int32_t reserved_;
+    uint64_t pixels;
+    uint64_t pixels_over; /* of the last check */
+    double max_rho, mean_rho; /* of the last check; the mean is of min(rho, 4096) in 2^-20 steps */
+    int32_t pass_samples[PTG_NOISE_MAX_PASSES];  /* samples done after pass k */
+    uint64_t pass_over[PTG_NOISE_MAX_PASSES];    /* pixels over the target after pass k */
+} ptg_noise_report;
+
+/* Render until the noise target is met, at most params->samples samples per
+ * sub-pixel.  Synchronous; params->shard_count must be 1.  Resets, then runs
+ * the passes of ptg_noise_schedule(target->min_samples, params->samples) with
+ * PTG_FLAG_MOMENTS; after each pass one ptg_noise_device check (stats only,
+ * 32 bytes copied back); stops when pixels over <= max_fraction * pixels.
+ * Then resolves and ADDS into image_rgb like the drop-in entry point: sample
+ * draws do not depend on params->samples, so the image equals that entry
+ * point's at samples = report->samples_done bit for bit.  report is optional. */
+int ptg_render_to_noise(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                        const ptg_params *params, int device, const ptg_noise_target *target, double *image_rgb,
+                        ptg_noise_report *report);
 
 /* Reassemble shard_count gathered slabs (rank-major, as all-gather lays them
  * out) into the width*height*3 image. */
