@@ -15,7 +15,11 @@
 //   * the grid is ceil(n_units / waves per workgroup);
 //   * decoded as the kernel decodes them, the units cover the samples
 //     [sample_begin, sample_end) of every pixel group (and pixel part)
-//     exactly once.
+//     exactly once;
+//   * the pixels of every unit, formed as render_unit forms them (x0, npix,
+//     left), fit the wave's 64 lanes, lie inside the row and inside their
+//     group's span, and every pixel of every slab row receives exactly
+//     sample_end - sample_begin samples.
 // Then it prints the plan and, for the three built-in scenes, the scene
 // fields of KArgs with a hash of the linear upload table; --dump prints both
 // as JSON, which the test compares with tests/golden/launch_plans.json.
@@ -103,6 +107,9 @@ static void check_plan(const char *name, const KArgs &A, int grid, bool bvh)
     // the sample chunks s_begin, s_begin + len, ... in order, up to s_end
     std::vector<int> next((size_t)A.n_groups * A.pixels_per_wave, A.sample_begin);
     std::vector<char> parts((size_t)A.n_groups, 0);
+    // ... and the pixels the unit covers, formed as render_unit forms them
+    // (slab_row, xblk, x0, npix, left): samples received per slab pixel
+    std::vector<int> got((size_t)A.slab_rows * A.W, 0);
     for (long long unit = 0; unit < (long long)grid * waves; ++unit) {
         if (unit >= A.n_units)
             continue;
@@ -130,7 +137,25 @@ static void check_plan(const char *name, const KArgs &A, int grid, bool bvh)
         const int cnt = A.sample_end - (int)s0 < len ? A.sample_end - (int)s0 : len;
         nx += cnt;
         parts[group] = (char)ps;
+        const int slab_row = group / A.waves_per_row;
+        const int xblk = group - slab_row * A.waves_per_row;
+        const int x0 = xblk * A.pixels_per_wave + part;
+        int npix = (A.pixels_per_wave - part + ps - 1) / ps;
+        const int left = A.W - x0 > 0 ? (A.W - x0 + ps - 1) / ps : 0;
+        npix = npix < left ? npix : left;
+        CHECK(slab_row >= 0 && slab_row < A.slab_rows, "unit %lld: slab row %d", unit, slab_row);
+        CHECK(npix >= 0 && npix * A.lanes_per_pixel <= 64, "unit %lld: %d pixels of %d lanes", unit, npix,
+              A.lanes_per_pixel);
+        for (int k = 0; k < npix; ++k) {
+            const int px = x0 + k * ps;
+            CHECK(px < A.W, "unit %lld: pixel %d outside the row", unit, px);
+            CHECK(px >= xblk * A.pixels_per_wave && px < (xblk + 1) * A.pixels_per_wave,
+                  "unit %lld: pixel %d outside group %d's span", unit, px, group);
+            got[(size_t)slab_row * A.W + px] += cnt;
+        }
     }
+    for (size_t i = 0; i < got.size(); ++i)
+        CHECK(got[i] == nsamp, "slab row %zu pixel %zu received %d of %d samples", i / A.W, i % A.W, got[i], nsamp);
     for (int g = 0; g < A.n_groups && nsamp > 0; ++g) {
         CHECK(parts[g] >= 1, "group %d has no unit", g);
         for (int k = 0; k < parts[g]; ++k)
@@ -292,6 +317,33 @@ int main(int argc, char **argv)
         {nullptr, 9, 8192, 400, 300, 64, 2, 1, 0, 1, 0, PTG_FLAG_EXACT_MATH, 0, -1, false, 0, PTG_OK});
     add("n10000 16384x16384x16 nsub8 chunk1",
         {nullptr, 10000, 8192, 16384, 16384, 16, 8, 1, 0, 1, 1, 0, 0, -1, false, 1, PTG_ERR_UNSUPPORTED});
+    // every unit-level kind away from nsub 2 (tests/test_gpu_frame_shapes.py runs these frames on the GPU)
+    struct Shape {
+        int n, nsub, W, H, samples;
+    };
+    for (const Shape &f : {Shape{9, 8, 128, 96, 8},      // split tail, accumulating: exactly 12,288 groups
+                           Shape{9, 8, 128, 95, 8},      // one row below it: a single level, 2 chunks of 4
+                           Shape{9, 8, 256, 160, 8},     // cooperative tail, 1 pixel per wave
+                           Shape{9, 5, 513, 160, 8},     // cooperative tail, 50 and 25 valid slots
+                           Shape{9, 5, 257, 96, 8},      // accumulating tail, 50 / 25 slots
+                           Shape{9, 3, 701, 122, 8},     // accumulating tail, 63 / 9 slots
+                           Shape{9, 6, 127, 97, 9},      // tail chunks 2, 2, 2, 2, 1; 36 slots
+                           Shape{9, 7, 129, 96, 8},      // 49 slots
+                           Shape{9, 1, 1000, 768, 8},    // the last group of a row has 40 of 64 pixels
+                           Shape{300, 3, 700, 246, 8},   // BVH tail that cannot pixel-split (7 < 8)
+                           Shape{300, 3, 700, 246, 9},   // BVH pixel split, 5 parts of 7 pixels
+                           Shape{300, 3, 700, 246, 13},  // BVH pixel split, 7 of 7
+                           Shape{300, 1, 1000, 1536, 8},  // BVH pixel split, 8 of 64, ragged last group
+                           Shape{300, 8, 192, 128, 8},   // BVH accumulating tail, 1 pixel per wave
+                           Shape{300, 8, 96, 64, 16}})   // BVH head/tail plan
+        add("n" + std::to_string(f.n) + " " + std::to_string(f.W) + "x" + std::to_string(f.H) + "x" +
+                std::to_string(f.samples) + " nsub" + std::to_string(f.nsub),
+            {nullptr, f.n, 8192, f.W, f.H, f.samples, f.nsub, 1, 0, 1, 0, 0, 0, -1, false, 1, PTG_OK});
+    // the last slab row of rank 1 lies outside the image
+    add("n9 129x191x8 nsub7 shard 2/2", {nullptr, 9, 8192, 129, 191, 8, 7, 1, 1, 2, 0, 0, 0, -1, false, 1, PTG_OK});
+    // 3-row bands over 2 shards, H no multiple of 6: slab rows past the image in the last band
+    add("n9 13x20x4 nsub5 band3 shard 2/2", {nullptr, 9, 8192, 13, 20, 4, 5, 3, 1, 2, 0, 0, 0, -1, false, 1, PTG_OK});
+    add("n300 9x20x4 nsub8 band3 shard 1/2", {nullptr, 300, 8192, 9, 20, 4, 8, 3, 0, 2, 0, 0, 0, -1, false, 1, PTG_OK});
     if (dump)
         std::printf("{\"plans\": [\n");
     for (size_t i = 0; i < rows.size() && !fails; ++i)

@@ -93,7 +93,11 @@ def _frame_coords(W, H, n, nsub):
 @pytest.mark.parametrize("name", list(FRAMES))
 def test_fast_render_kernel_equals_fast_trace_kernel(name):
     _require_gpu()
-    W, H, n, nsub, passes = FRAMES[name]
+    check_render_equals_trace(name, *FRAMES[name])
+
+
+def check_render_equals_trace(name, W, H, n, nsub, passes):
+    """The identity of (a) on one frame (also used by tests/test_gpu_frame_shapes.py)."""
     p = ptgpu.make_params(W, H, n, nsub, SEED, flags=MOM)
     plain = ptgpu.make_params(W, H, n, nsub, SEED)
     coords = _frame_coords(W, H, n, nsub)

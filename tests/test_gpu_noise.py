@@ -222,8 +222,12 @@ def test_raw_moments_and_stats_of_three_shards():
 def test_slabs_match_the_definition(case):
     _require_gpu()
     name, W, H, n, nsub, passes = CASES[case]
+    check_slabs(case, name, W, H, n, nsub, _params(case))
+
+
+def check_slabs(case, name, W, H, n, nsub, p):
+    """The module's criterion on one frame (also used by tests/test_gpu_frame_shapes.py)."""
     E = _paths(name, W, H, n, nsub)
-    p = _params(case)
     with ptgpu.Context(*_scene(name, W, H)) as ctx:
         for done in sorted({n, max(2, n // 2 + 1)}):  # the full count and a partial one
             _accumulate(ctx, p, [(0, done)])

@@ -41,21 +41,26 @@ def _arrays(scn):
                                             ("simple", 400, 300, 16), ("synthetic:300", 48, 27, 4)])
 def test_reference_f64_matches_mode_a_xs(name, W, H, samps):
     _require_gpu()
+    check_matches_mode_a_xs(name, W, H, samps)
+
+
+def check_matches_mode_a_xs(name, W, H, samps, nsub=2):
+    """The module's criterion on one frame (also used by tests/test_gpu_frame_shapes.py)."""
     scn = ptgpu.make_scene(name, W, H)
     cam, sp, ca = _arrays(scn)
     img = np.zeros((H * W, 3))
-    ptgpu.render(scn, cam, img, W, H, samps, flags=ptgpu.FLAG_REFERENCE_F64)
-    ref, rsegs = po.render_xs_f64(sp, ca, W, H, samps, 2, SEED, nthreads=NT)
+    ptgpu.render(scn, cam, img, W, H, samps, nsub, SEED, flags=ptgpu.FLAG_REFERENCE_F64)
+    ref, rsegs = po.render_xs_f64(sp, ca, W, H, samps, nsub, SEED, nthreads=NT)
     d = np.abs(img.reshape(H, W, 3) - ref)
     exact = float((d.max(axis=2) == 0).mean())
-    print(f"{name} {W}x{H}x{4 * samps}: max |diff| {d.max():.3e}, pixels bit-identical {100 * exact:.2f} %")
+    print(f"{name} {W}x{H}x{nsub * nsub * samps}: max |diff| {d.max():.3e}, pixels bit-identical {100 * exact:.2f} %")
     assert d.max() <= 1e-9, d.max()
     assert exact > 0.99
     # segment counts through the device path (float slab)
     out = torch.zeros(H * W * 3, dtype=torch.float32, device="cuda")
     segs = torch.zeros(1, dtype=torch.int64, device="cuda")
     with ptgpu.Context(scn, cam) as ctx:
-        ctx.render_device(out, ptgpu.make_params(W, H, samps, flags=ptgpu.FLAG_REFERENCE_F64), segs)
+        ctx.render_device(out, ptgpu.make_params(W, H, samps, nsub, SEED, flags=ptgpu.FLAG_REFERENCE_F64), segs)
         torch.cuda.synchronize()
     assert int(segs.item()) == rsegs
     assert np.array_equal(out.cpu().numpy().reshape(H, W, 3), ref.astype(np.float32))

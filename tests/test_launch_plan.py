@@ -48,6 +48,11 @@ def test_launch_plan_invariants(check_exe):
     assert "n10000 1920x1080x1024: grid=187560" in out
     assert "n10000 1920x1080x1024 shard 1/8: grid=150600 units=150600" in out
     assert "too many work units" in out
+    # level kinds away from nsub 2 (tests/test_gpu_frame_shapes.py runs them on the GPU)
+    assert "n9 128x96x8 nsub8: grid=17408 units=69632 levels=2 resolve_row0=32" in out
+    assert "n9 128x95x8 nsub8: grid=6080 units=24320 levels=1" in out
+    assert "n300 700x246x8 nsub3: grid=82000 units=82000 levels=2 resolve_row0=164" in out
+    assert "n300 700x246x9 nsub3: grid=57400 units=57400 levels=2 resolve_row0=-1" in out
 
 
 @pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not present")
