@@ -1184,7 +1184,9 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         f3 v1 = isD ? uu : d;
         const float r1 = Math<kExact>::rsqrt(dot3(v1, v1));
         v1 = mk3(v1.x * r1, v1.y * r1, v1.z * r1);
-        const float x0 = -dot3(v1, nn);
+        // (fast mode: only dielectric lanes read x0, and there v1 = d r1, so
+        // v1.nn = (nn.d) r1 = kn r1 -- the dot the mirror already uses)
+        const float x0 = kExact ? -dot3(v1, nn) : -(kn * r1);
         // fast mode: one v_min_f32 (differs from the select only for NaN)
         const float cthG = kExact ? (1.0f < x0 ? 1.0f : x0) : __builtin_fminf(1.0f, x0);  // main.cpp:77
         // op2: diffuse -> sin theta = sqrt(r); dielectric -> sin theta = sqrt(1 - cos^2)
@@ -1195,8 +1197,10 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         const float s2 = kExact ? Math<kExact>::sqrt0(isD ? ra : __builtin_fmaf(-cthG, cthG, 1.0f))
                                 : Math<kExact>::sqrt(isD ? ra : __builtin_fmaf(-cthG, cthG, 1.0f));
         const float ratio = front ? 0.5f : 2.0f;  // main.cpp:72
+        // fast mode: ratio sin theta once, for the refraction test and |r_out_perp| below
+        [[maybe_unused]] const float rs2 = kExact ? 0.0f : ratio * s2;
         if (isG) {
-            bool reflect = ratio * s2 > 1.0f;  // cannot refract: no Fresnel draw (main.cpp:89)
+            bool reflect = (kExact ? ratio * s2 : rs2) > 1.0f;  // cannot refract: no Fresnel draw (main.cpp:89)
             if (!reflect) {
                 const float r0 = 0x1.c71c74p-4f;  // ((1-ratio)/(1+ratio))^2, equal for ratio 0.5 and 2
                 float xm = 1.0f - cthG;
@@ -1216,7 +1220,19 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         // op3: diffuse -> cos theta = sqrt(1 - r); dielectric -> |r_out_parallel| (main.cpp:94)
         const f3 perp = mk3(__builtin_fmaf(nn.x, cthG, v1.x) * ratio, __builtin_fmaf(nn.y, cthG, v1.y) * ratio,
                             __builtin_fmaf(nn.z, cthG, v1.z) * ratio);
-        const float s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(1.0f - dot3(perp, perp)));  // both >= 0
+        // (fast mode: nn and v1 are unit and v1.nn = -cos theta, so
+        // |perp|^2 = ratio^2 (1 - cos^2 theta) = rs2^2 -- one fma for the dot
+        // and its subtraction.  The one assumption added: cthG is the
+        // un-clamped x0 wherever the clamp does not bind, which is where s2^2
+        // is 1 - x0^2; then rs2^2 and |perp|^2 differ by roundings only.
+        // Where it binds, cthG = 1 and s2 = 0: the argument is 1, perp is
+        // within rounding of 0.)
+        float s3;  // both arguments >= 0
+        if constexpr (!kExact) {
+            const float gq = __builtin_fmaf(-rs2, rs2, 1.0f);
+            s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(gq));
+        } else
+        s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(1.0f - dot3(perp, perp)));
         if (isD) {  // main.cpp:53-55 (unit by construction, not re-normalised)
             f3 vv = cross3(nn, v1);
             float cs = cp * s2, ss = sp * s2;
