@@ -298,4 +298,40 @@ inline int fill_launch(const KArgs &base, int wave_slots, const ptg_params *p, K
     return PTG_OK;
 }
 
+// An adaptive pass (ptg_accumulate_active_device): `units` work units of the
+// active list (the caller's bound on them) x chunks of the add_samples new
+// samples, chunk-major; unit k of chunk c is wave units * c + k of the grid
+// when all `units` are active (the kernel takes the true count from the
+// device).  chunk_samples is honoured, else the auto rule applies to the unit
+// count; every chunk is within kMaxChunk.
+struct ActivePlan {
+    int chunk;          // samples per unit
+    int n_chunks;       // ceil(add_samples / chunk)
+    long long n_units;  // units * n_chunks
+    int grid;           // workgroups
+};
+inline int plan_active(bool bvh, int wave_slots, long long units, int add_samples, int chunk_samples, ActivePlan &P)
+{
+    P = ActivePlan{1, 0, 0, 0};
+    if (units <= 0 || add_samples <= 0)
+        return PTG_OK;  // nothing to launch
+    int chunk = chunk_samples;
+    if (chunk <= 0)
+        chunk = plan_auto_chunk(bvh, wave_slots, (int)(units < 0x7FFFFFFFLL ? units : 0x7FFFFFFFLL), add_samples);
+    if (chunk > add_samples)
+        chunk = add_samples;
+    if (chunk > kMaxChunk)
+        chunk = kMaxChunk;
+    P.chunk = chunk;
+    P.n_chunks = (add_samples + chunk - 1) / chunk;
+    P.n_units = units * P.n_chunks;  // units <= 2^31, n_chunks <= 2^30: no overflow in 64 bits
+    const int waves_per_block = (bvh ? PTG_BVH_BLOCK : kBlock) / 64;
+    const long long g = (P.n_units + waves_per_block - 1) / waves_per_block;  // 64-bit before any cast
+    if (g > 0x7FFFFFFFLL)
+        return fail(PTG_ERR_UNSUPPORTED, "too many work units (" + std::to_string(P.n_units) +
+                                             "): raise chunk_samples or use 0 (auto)");
+    P.grid = (int)g;
+    return PTG_OK;
+}
+
 }  // namespace

@@ -1308,8 +1308,25 @@ __device__ __forceinline__ unsigned long long quant(float c)
 // passes with PTG_FLAG_MOMENTS): every finished path also adds
 // quant(cl(c) * cl(c)) of its components to a second per-slot LDS sum, added
 // to the second HBM accumulator acc2 (laid out like A.acc) at unit end.
-template <bool kCount, bool kBvh, bool kExact, bool kMoments>
-__device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *const acc2)
+//
+// kGather (gather_kernel, ptg_accumulate_active_device): the unit's pixels are
+// an entry of the active list's unit table instead of a pixel group -- up to
+// pixels_per_wave active pixels of one slab row, anywhere in the row.  Pixel p
+// already holds n_p samples (the count slab); its slots' keys are shifted by
+// n_p G once here, so that the unit's local samples [0, add_samples) draw what
+// samples [n_p, n_p + add_samples) draw unshifted (sample_state(key + b G, s)
+// == sample_state(key, b + s)); the main loop is the same.
+struct GatherArgs {
+    const int4 *units;              // unit table: {slab row, first index in the row's list, pixels, 0}
+    const int *list;                // per slab row (stride W) its active x, ascending
+    const int *counts;              // per slab pixel the samples it holds
+    const unsigned long long *rec;  // device record {active pixels, active units}
+    long long max_units;            // the launch covers units [0, min(rec[1], max_units)) ...
+    int n_chunks;                   // ... x n_chunks chunks of lvl_chunk[0] samples, chunk-major
+};
+template <bool kCount, bool kBvh, bool kExact, bool kMoments, bool kGather = false>
+__device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *const acc2,
+                                            const GatherArgs G = GatherArgs{})
 {
     constexpr int kWaves = kBlockOf<kBvh> / 64;
     __shared__ unsigned long long lds_acc[kWaves][64 * 3];
@@ -1373,7 +1390,25 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     const int group = A.lvl_group[lv] + (int)(coop ? tg : tg % nlg);
     const int part = coop ? 0 : (int)(tg / nlg);
     const int len = A.lvl_chunk[lv];
-    const int s0 = A.sample_begin + (int)(coop ? t % kWaves : t / nlu) * len;
+    int s0 = A.sample_begin + (int)(coop ? t % kWaves : t / nlu) * len;
+    int4 ent = make_int4(0, 0, 0, 0);
+    if constexpr (kGather) {
+        // the true unit count is the device's (scalar loads, like the table
+        // entry: everything here is wave-uniform); a wave past it exits
+        long long n_au = (long long)G.rec[1];
+        n_au = n_au < G.max_units ? n_au : G.max_units;
+        if (unit >= n_au * G.n_chunks)
+            return;  // whole wave
+        // (the 64-bit division runs on the vector unit: its results back to SGPRs)
+        const long long cq = unit / n_au;
+        const int c = __builtin_amdgcn_readfirstlane((int)cq);                // < n_chunks
+        const int u = __builtin_amdgcn_readfirstlane((int)(unit - cq * n_au));  // < n_au <= n_groups
+        ent = G.units[u];
+        ent.x = __builtin_amdgcn_readfirstlane(ent.x);
+        ent.y = __builtin_amdgcn_readfirstlane(ent.y);
+        ent.z = __builtin_amdgcn_readfirstlane(ent.z);
+        s0 = c * len;  // local samples [0, add_samples) = [sample_begin, sample_end)
+    }
     if (s0 >= A.sample_end)
         return;  // whole wave: alignment padding before a cooperative level
 #if PTG_UNIT_TRACE
@@ -1381,7 +1416,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
 #endif
     // the unit holds every sample of its pixels: resolve in the wave
     const bool in_wave = A.lvl_inwave[lv] != 0;
-    const int slab_row = group / A.waves_per_row;
+    const int slab_row = kGather ? ent.x : group / A.waves_per_row;
     const int xblk = group - slab_row * A.waves_per_row;
     const int r = out_row_of(A, slab_row);
     const int y = A.H - 1 - r;  // main.cpp:181: y = 0 is the bottom row
@@ -1390,6 +1425,8 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     int npix = (A.pixels_per_wave - part + ps - 1) / ps;
     const int left = A.W - x0 > 0 ? (A.W - x0 + ps - 1) / ps : 0;
     npix = npix < left ? npix : left;
+    if constexpr (kGather)
+        npix = ent.z;  // (x0 is not used: the slots' x come from the list)
     const int nv = r < A.H ? npix * A.lanes_per_pixel : 0;  // valid slots are a prefix
     int cnt = A.sample_end - s0;
     cnt = cnt < len ? cnt : len;
@@ -1405,11 +1442,16 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     }
     if (lane < nv) {
         int px = x0 + (lane / A.lanes_per_pixel) * ps;
+        if constexpr (kGather)
+            px = G.list[(size_t)slab_row * A.W + ent.y + lane / A.lanes_per_pixel];
         int sub = lane % A.lanes_per_pixel;
         int sy = sub / A.nsub;
         int sx = sub - sy * A.nsub;
         const uint64_t pix_sub = ((uint64_t)y * (uint64_t)A.W + (uint64_t)px) * (uint64_t)A.lanes_per_pixel + (uint64_t)sub;
-        lds_key[wv][lane] = key_hash(A.seed, pix_sub);
+        uint64_t key = key_hash(A.seed, pix_sub);
+        if constexpr (kGather)
+            key += (uint64_t)(uint32_t)G.counts[(size_t)slab_row * A.W + px] * 0x9E3779B97F4A7C15ull;
+        lds_key[wv][lane] = key;
         lds_pix[wv][lane] = (uint32_t)px | ((uint32_t)sx << 20) | ((uint32_t)sy << 26);
     }
     __builtin_amdgcn_wave_barrier();
@@ -1893,12 +1935,19 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         int ln = lane_e, row = slab_row, px0 = x0;
         asm volatile("" : "+v"(ln), "+s"(row), "+s"(px0));
         unsigned long long *g = A.acc + (((size_t)row * A.W + px0) * A.lanes_per_pixel + ln) * 3;
+        size_t gi = 0;
+        if constexpr (kGather) {  // each slot's own pixel
+            gi = ((size_t)row * A.W + (lds_pix[wv][ln] & 0xFFFFFu)) * A.lanes_per_pixel + ln % A.lanes_per_pixel;
+            g = A.acc + gi * 3;
+        }
         unsigned long long vx = lds_acc[wv][ln], vy = lds_acc[wv][ln + 64], vz = lds_acc[wv][ln + 128];
         if (vx) atomicAdd(g + 0, vx);
         if (vy) atomicAdd(g + 1, vy);
         if (vz) atomicAdd(g + 2, vz);
         if constexpr (kMoments) {
             unsigned long long *g2 = acc2 + (((size_t)row * A.W + px0) * A.lanes_per_pixel + ln) * 3;
+            if constexpr (kGather)
+                g2 = acc2 + gi * 3;
             const unsigned long long wx = lds_acc2[wv][ln], wy = lds_acc2[wv][ln + 64], wz = lds_acc2[wv][ln + 128];
             if (wx) atomicAdd(g2 + 0, wx);
             if (wy) atomicAdd(g2 + 1, wy);
@@ -1925,8 +1974,39 @@ __global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void moments_ke
     render_unit<kCount, kBvh, kExact, true>(A, acc2);
 }
 
-// main.cpp:195-196: per pixel, the clamped sub-pixel means added with weight
-// 1/nsub^2 in (sy, sx) order; re-zeroes the accumulator for the next frame.
+// Adaptive passes (ptg_accumulate_active_device): the units of the active
+// list, both moments summed, every unit accumulates in HBM.
+template <bool kBvh, bool kExact, bool kCount = false>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void gather_kernel(KArgs A, unsigned long long *acc2,
+                                                                                   GatherArgs G)
+{
+    render_unit<kCount, kBvh, kExact, true, true>(A, acc2, G);
+}
+
+// The pixel value from the exact sums g of its sub-pixels after samps samples
+// (main.cpp:195-196): the clamped sub-pixel means added with weight 1/nsub^2
+// in (sy, sx) order.  Shared by resolve_kernel (one samps for the slab) and
+// resolve_active_kernel (each pixel's own count).
+__device__ __forceinline__ f3 resolve_pixel(const KArgs &A, unsigned long long *g, const int &samps, const int &keep)
+{
+    f3 pix = mk3(0.0f, 0.0f, 0.0f);
+    for (int j = 0; j < A.lanes_per_pixel; ++j) {
+        float m[3];
+        for (int c = 0; c < 3; ++c) {
+            unsigned long long sum = g[3 * j + c];
+            if (!keep)
+                g[3 * j + c] = 0ull;
+            float mean = samps > 0 ? (float)(((double)sum * 0x1p-32) / (double)samps) : 0.0f;
+            m[c] = mean < 0.0f ? 0.0f : (1.0f < mean ? 1.0f : mean);
+        }
+        pix = mk3(__builtin_fmaf(m[0], A.inv_sub2, pix.x), __builtin_fmaf(m[1], A.inv_sub2, pix.y),
+                  __builtin_fmaf(m[2], A.inv_sub2, pix.z));
+    }
+    return pix;
+}
+
+// main.cpp:195-196 per pixel (resolve_pixel); re-zeroes the accumulator for
+// the next frame.
 __global__ __launch_bounds__(256) void resolve_kernel(KArgs A)
 {
     const long long i = (long long)A.resolve_row0 * A.W + (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1936,88 +2016,69 @@ __global__ __launch_bounds__(256) void resolve_kernel(KArgs A)
     if (out_row_of(A, slab_row) >= A.H)
         return;
     unsigned long long *g = A.acc + (size_t)i * A.lanes_per_pixel * 3;
-    f3 pix = mk3(0.0f, 0.0f, 0.0f);
-    for (int j = 0; j < A.lanes_per_pixel; ++j) {
-        float m[3];
-        for (int c = 0; c < 3; ++c) {
-            unsigned long long sum = g[3 * j + c];
-            if (!A.keep_acc)
-                g[3 * j + c] = 0ull;
-            float mean = A.samps > 0 ? (float)(((double)sum * 0x1p-32) / (double)A.samps) : 0.0f;
-            m[c] = mean < 0.0f ? 0.0f : (1.0f < mean ? 1.0f : mean);
-        }
-        pix = mk3(__builtin_fmaf(m[0], A.inv_sub2, pix.x), __builtin_fmaf(m[1], A.inv_sub2, pix.y),
-                  __builtin_fmaf(m[2], A.inv_sub2, pix.z));
-    }
+    const f3 pix = resolve_pixel(A, g, A.samps, A.keep_acc);
     float *out = A.out + (size_t)i * 3;
     out[0] = pix.x;
     out[1] = pix.y;
     out[2] = pix.z;
 }
 
-// ptg_noise_device (include/ptgpu.h "per-pixel noise estimates"): one thread
-// per slab pixel (grid-stride), from the exact sums A.acc (S1) and acc2 (S2)
-// after A.samps samples: the pixel value p as resolve_kernel computes it, per
-// channel the variance V of that value (every sub-pixel's variance of the
-// mean capped at 1/4: the image clamps the mean to [0, 1]) and the relative
-// standard error rho = sqrt(mean V) / max(mean p, floor); var / rho / stats
-// are optional.  stats: four integers, reduced per thread, per wave and per
-// workgroup (LDS), then one vector atomic per workgroup and value -- the
-// result does not depend on any order, and the grid is small enough
-// (ptg_noise_device: at most kNoiseBlocks workgroups) that the atomics on the
-// one cache line do not set the time (one per wave of a 1920x1080 frame:
-// 1.58 ms, against 0.22 ms without the stats).
-constexpr int kNoiseBlocks = 2048;  // 8 workgroups of 256 per CU on 256 CUs
-__global__ __launch_bounds__(256) void noise_kernel(KArgs A, const unsigned long long *__restrict__ acc2,
-                                                    double rel_error, double floor, float *__restrict__ var,
-                                                    float *__restrict__ rho_out, unsigned long long *stats)
+// ptg_resolve_active_device: resolve_kernel's arithmetic with each pixel's
+// own sample count (0 samples: 0); the sums are kept.
+__global__ __launch_bounds__(256) void resolve_active_kernel(KArgs A, const int *__restrict__ counts)
 {
-    const long long total = (long long)A.slab_rows * A.W;
-    const long long stride = (long long)gridDim.x * 256;
-    unsigned over = 0u, cnt = 0u, rho_bits = 0u;
-    unsigned long long fixed = 0ull;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        if (out_row_of(A, (int)(i / A.W)) >= A.H)
-            continue;  // a slab row past the image
-        const unsigned long long *g1 = A.acc + (size_t)i * A.lanes_per_pixel * 3;
-        const unsigned long long *g2 = acc2 + (size_t)i * A.lanes_per_pixel * 3;
-        const double n = (double)A.samps;
-        f3 pix = mk3(0.0f, 0.0f, 0.0f);
-        double vs[3] = {0.0, 0.0, 0.0};
-        for (int j = 0; j < A.lanes_per_pixel; ++j) {
-            float m[3];
-            for (int c = 0; c < 3; ++c) {
-                const double m1 = ((double)g1[3 * j + c] * 0x1p-32) / n;
-                const double m2 = ((double)g2[3 * j + c] * 0x1p-32) / n;
-                const float mean = (float)m1;
-                m[c] = mean < 0.0f ? 0.0f : (1.0f < mean ? 1.0f : mean);
-                double v = m2 - m1 * m1;
-                v = (v > 0.0 ? v : 0.0) / (n - 1.0);
-                vs[c] += v < 0.25 ? v : 0.25;
-            }
-            pix = mk3(__builtin_fmaf(m[0], A.inv_sub2, pix.x), __builtin_fmaf(m[1], A.inv_sub2, pix.y),
-                      __builtin_fmaf(m[2], A.inv_sub2, pix.z));
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)A.slab_rows * A.W)
+        return;
+    if (out_row_of(A, (int)(i / A.W)) >= A.H)
+        return;
+    const int np = counts[i], keep = 1;
+    const f3 pix = resolve_pixel(A, A.acc + (size_t)i * A.lanes_per_pixel * 3, np, keep);
+    float *out = A.out + (size_t)i * 3;
+    out[0] = pix.x;
+    out[1] = pix.y;
+    out[2] = pix.z;
+}
+
+// include/ptgpu.h "per-pixel noise estimates": from a pixel's exact sums g1
+// (S1) and g2 (S2) after n >= 2 samples, the variance V[3] of its value and
+// its relative standard error.  Shared by noise_kernel (one n for the slab)
+// and select_over_kernel (each pixel's own count).
+__device__ __forceinline__ float noise_pixel(const KArgs &A, const unsigned long long *g1,
+                                             const unsigned long long *g2, const double n, const double floor,
+                                             double V[3])
+{
+    f3 pix = mk3(0.0f, 0.0f, 0.0f);
+    double vs[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < A.lanes_per_pixel; ++j) {
+        float m[3];
+        for (int c = 0; c < 3; ++c) {
+            const double m1 = ((double)g1[3 * j + c] * 0x1p-32) / n;
+            const double m2 = ((double)g2[3 * j + c] * 0x1p-32) / n;
+            const float mean = (float)m1;
+            m[c] = mean < 0.0f ? 0.0f : (1.0f < mean ? 1.0f : mean);
+            double v = m2 - m1 * m1;
+            v = (v > 0.0 ? v : 0.0) / (n - 1.0);
+            vs[c] += v < 0.25 ? v : 0.25;
         }
-        const double w = (double)A.inv_sub2 * (double)A.inv_sub2;
-        const double V[3] = {w * vs[0], w * vs[1], w * vs[2]};
-        if (var) {
-            var[(size_t)i * 3 + 0] = (float)V[0];
-            var[(size_t)i * 3 + 1] = (float)V[1];
-            var[(size_t)i * 3 + 2] = (float)V[2];
-        }
-        const double sigma = __builtin_sqrt((V[0] + V[1] + V[2]) / 3.0);
-        const double mu = ((double)pix.x + (double)pix.y + (double)pix.z) / 3.0;
-        const float rho = (float)(sigma / (mu > floor ? mu : floor));
-        if (rho_out)
-            rho_out[i] = rho;
-        over += (double)rho > rel_error ? 1u : 0u;
-        fixed += (unsigned long long)((rho < 4096.0f ? rho : 4096.0f) * 0x1p20f);
-        const unsigned bits = __float_as_uint(rho);  // rho >= 0: the bit patterns order like the values
-        rho_bits = rho_bits > bits ? rho_bits : bits;
-        cnt += 1u;
+        pix = mk3(__builtin_fmaf(m[0], A.inv_sub2, pix.x), __builtin_fmaf(m[1], A.inv_sub2, pix.y),
+                  __builtin_fmaf(m[2], A.inv_sub2, pix.z));
     }
-    if (!stats)
-        return;  // the whole grid
+    const double w = (double)A.inv_sub2 * (double)A.inv_sub2;
+    V[0] = w * vs[0];
+    V[1] = w * vs[1];
+    V[2] = w * vs[2];
+    const double sigma = __builtin_sqrt((V[0] + V[1] + V[2]) / 3.0);
+    const double mu = ((double)pix.x + (double)pix.y + (double)pix.z) / 3.0;
+    return (float)(sigma / (mu > floor ? mu : floor));
+}
+
+// The four statistics of ptg_noise_device, reduced per wave and per workgroup
+// (LDS), then one vector atomic per workgroup and value; every thread of the
+// workgroup calls it.
+__device__ __forceinline__ void reduce_noise_stats(unsigned over, unsigned cnt, unsigned long long fixed,
+                                                   unsigned rho_bits, unsigned long long *stats)
+{
     for (int off = 32; off > 0; off >>= 1) {  // every lane of the wave takes part
         over += __shfl_xor(over, off, 64);
         cnt += __shfl_xor(cnt, off, 64);
@@ -2047,6 +2108,236 @@ __global__ __launch_bounds__(256) void noise_kernel(KArgs A, const unsigned long
             atomicAdd(stats + 1, t[1]);
             atomicMax(stats + 2, t[2]);
             atomicAdd(stats + 3, t[3]);
+        }
+    }
+}
+
+// ptg_noise_device (include/ptgpu.h "per-pixel noise estimates"): one thread
+// per slab pixel (grid-stride), from the exact sums A.acc (S1) and acc2 (S2)
+// after A.samps samples: the pixel value p as resolve_kernel computes it, per
+// channel the variance V of that value (every sub-pixel's variance of the
+// mean capped at 1/4: the image clamps the mean to [0, 1]) and the relative
+// standard error rho = sqrt(mean V) / max(mean p, floor); var / rho / stats
+// are optional.  stats: four integers, reduced per thread, per wave and per
+// workgroup (LDS), then one vector atomic per workgroup and value -- the
+// result does not depend on any order, and the grid is small enough
+// (ptg_noise_device: at most kNoiseBlocks workgroups) that the atomics on the
+// one cache line do not set the time (one per wave of a 1920x1080 frame:
+// 1.58 ms, against 0.22 ms without the stats).
+constexpr int kNoiseBlocks = 2048;  // 8 workgroups of 256 per CU on 256 CUs
+__global__ __launch_bounds__(256) void noise_kernel(KArgs A, const unsigned long long *__restrict__ acc2,
+                                                    double rel_error, double floor, float *__restrict__ var,
+                                                    float *__restrict__ rho_out, unsigned long long *stats)
+{
+    const long long total = (long long)A.slab_rows * A.W;
+    const long long stride = (long long)gridDim.x * 256;
+    unsigned over = 0u, cnt = 0u, rho_bits = 0u;
+    unsigned long long fixed = 0ull;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (out_row_of(A, (int)(i / A.W)) >= A.H)
+            continue;  // a slab row past the image
+        const unsigned long long *g1 = A.acc + (size_t)i * A.lanes_per_pixel * 3;
+        const unsigned long long *g2 = acc2 + (size_t)i * A.lanes_per_pixel * 3;
+        double V[3];
+        const float rho = noise_pixel(A, g1, g2, (double)A.samps, floor, V);
+        if (var) {
+            var[(size_t)i * 3 + 0] = (float)V[0];
+            var[(size_t)i * 3 + 1] = (float)V[1];
+            var[(size_t)i * 3 + 2] = (float)V[2];
+        }
+        if (rho_out)
+            rho_out[i] = rho;
+        over += (double)rho > rel_error ? 1u : 0u;
+        fixed += (unsigned long long)((rho < 4096.0f ? rho : 4096.0f) * 0x1p20f);
+        const unsigned bits = __float_as_uint(rho);  // rho >= 0: the bit patterns order like the values
+        rho_bits = rho_bits > bits ? rho_bits : bits;
+        cnt += 1u;
+    }
+    if (!stats)
+        return;  // the whole grid
+    reduce_noise_stats(over, cnt, fixed, rho_bits, stats);
+}
+
+// ---- adaptive sampling: the active list (include/ptgpu.h "adaptive sampling") ----
+// ptg_select_active_device, step 1: noise_kernel with each pixel's own sample
+// count n_p (n_p < 2: rho = +inf) -- per slab pixel a byte "over the target"
+// (0 in rows past the image, so step 2 may read any row), optionally rho, and
+// the four statistics.
+__global__ __launch_bounds__(256) void select_over_kernel(KArgs A, const unsigned long long *__restrict__ acc2,
+                                                          const int *__restrict__ counts, double rel_error,
+                                                          double floor, uint8_t *__restrict__ over_out,
+                                                          float *__restrict__ rho_out, unsigned long long *stats)
+{
+    const long long total = (long long)A.slab_rows * A.W;
+    const long long stride = (long long)gridDim.x * 256;
+    unsigned over = 0u, cnt = 0u, rho_bits = 0u;
+    unsigned long long fixed = 0ull;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (out_row_of(A, (int)(i / A.W)) >= A.H) {
+            over_out[i] = 0;
+            continue;  // a slab row past the image
+        }
+        const int np = counts[i];
+        float rho = __builtin_inff();
+        if (np >= 2) {
+            double V[3];
+            rho = noise_pixel(A, A.acc + (size_t)i * A.lanes_per_pixel * 3, acc2 + (size_t)i * A.lanes_per_pixel * 3,
+                              (double)np, floor, V);
+        }
+        if (rho_out)
+            rho_out[i] = rho;
+        const unsigned is_over = (double)rho > rel_error ? 1u : 0u;
+        over_out[i] = (uint8_t)is_over;
+        over += is_over;
+        fixed += (unsigned long long)((rho < 4096.0f ? rho : 4096.0f) * 0x1p20f);
+        const unsigned bits = __float_as_uint(rho);
+        rho_bits = rho_bits > bits ? rho_bits : bits;
+        cnt += 1u;
+    }
+    if (!stats)
+        return;  // the whole grid
+    reduce_noise_stats(over, cnt, fixed, rho_bits, stats);
+}
+
+// List building, step 1: one workgroup per slab row writes the row's active x
+// in ascending order to list[row * W ...] and their number to row_count[row].
+// Active: flags == NULL, or some flag byte of the pixel's (2 dilate + 1)^2
+// window, clipped to the image, is set (dilate > 0 only with shard_count 1,
+// where slab row j is image row j).  Ranks: ballot / mbcnt within a wave, the
+// waves' counts through LDS -- the order does not depend on any timing.
+__global__ __launch_bounds__(256) void list_rows_kernel(KArgs A, const uint8_t *__restrict__ flags, int dilate,
+                                                        int *__restrict__ list, int *__restrict__ row_count)
+{
+    const int row = blockIdx.x;
+    const bool valid_row = out_row_of(A, row) < A.H;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ int wave_cnt[4];
+    int base = 0;  // the row's active pixels left of this tile (workgroup-uniform)
+    for (int x0 = 0; x0 < A.W; x0 += 256) {
+        const int x = x0 + (int)threadIdx.x;
+        bool act = false;
+        if (valid_row && x < A.W) {
+            if (!flags) {
+                act = true;
+            } else if (dilate == 0) {
+                act = flags[(size_t)row * A.W + x] != 0;
+            } else {
+                const int r0 = row - dilate > 0 ? row - dilate : 0;
+                const int r1 = row + dilate < A.H - 1 ? row + dilate : A.H - 1;
+                const int c0 = x - dilate > 0 ? x - dilate : 0;
+                const int c1 = x + dilate < A.W - 1 ? x + dilate : A.W - 1;
+                for (int rr = r0; rr <= r1; ++rr)
+                    for (int cc = c0; cc <= c1; ++cc)
+                        act |= flags[(size_t)rr * A.W + cc] != 0;
+            }
+        }
+        const unsigned long long m = __ballot(act);
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (lane == 0)
+            wave_cnt[wv] = (int)__popcll(m);
+        __syncthreads();
+        int before = 0, tile = 0;
+        for (int w = 0; w < 4; ++w) {
+            const int c = wave_cnt[w];
+            before += w < wv ? c : 0;
+            tile += c;
+        }
+        if (act)
+            list[(size_t)row * A.W + base + before + rank] = x;  // base + before + rank < the row's count <= W
+        base += tile;
+        __syncthreads();  // wave_cnt is rewritten by the next tile
+    }
+    if (threadIdx.x == 0)
+        row_count[row] = base;
+}
+
+// Step 2, one workgroup: a row's pixels are cut into units of pixels_per_wave
+// (units never span rows); row_unit0[row] = the units of the rows before it
+// (an exclusive scan: shuffles within a wave, LDS across the workgroup, a
+// carry across tiles of 256 rows).  Writes the device record {active pixels,
+// active units}, the same two values to info (optional), and adds them to
+// stats[4], stats[5] (optional).
+__global__ __launch_bounds__(256) void list_units_kernel(int slab_rows, int ppw, const int *__restrict__ row_count,
+                                                         int *__restrict__ row_unit0, unsigned long long *rec,
+                                                         unsigned long long *info, unsigned long long *stats)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ int wave_sum[4];
+    __shared__ unsigned long long wave_pix[4];
+    unsigned long long pixels = 0ull;
+    int carry = 0;
+    for (int r0 = 0; r0 < slab_rows; r0 += 256) {
+        const int r = r0 + (int)threadIdx.x;
+        const int cnt = r < slab_rows ? row_count[r] : 0;
+        const int nu = (cnt + ppw - 1) / ppw;
+        pixels += (unsigned long long)cnt;
+        int incl = nu;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int v = __shfl_up(incl, off, 64);
+            incl += lane >= off ? v : 0;
+        }
+        if (lane == 63)
+            wave_sum[wv] = incl;
+        __syncthreads();
+        int before = 0, tile = 0;
+        for (int w = 0; w < 4; ++w) {
+            const int c = wave_sum[w];
+            before += w < wv ? c : 0;
+            tile += c;
+        }
+        if (r < slab_rows)
+            row_unit0[r] = carry + before + incl - nu;
+        carry += tile;
+        __syncthreads();
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        pixels += __shfl_xor(pixels, off, 64);
+    if (lane == 0)
+        wave_pix[wv] = pixels;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long np = wave_pix[0] + wave_pix[1] + wave_pix[2] + wave_pix[3];
+        rec[0] = np;
+        rec[1] = (unsigned long long)carry;
+        if (info) {
+            info[0] = np;
+            info[1] = (unsigned long long)carry;
+        }
+        if (stats) {
+            atomicAdd(stats + 4, np);
+            atomicAdd(stats + 5, (unsigned long long)carry);
+        }
+    }
+}
+
+// Step 3, one workgroup per slab row: the row's entries of the unit table,
+// {slab row, first index in the row's list, pixels}.  The entries written are
+// [0, rec[1]), at most n_groups (the table's size).
+__global__ __launch_bounds__(256) void list_fill_kernel(int ppw, const int *__restrict__ row_count,
+                                                        const int *__restrict__ row_unit0, int4 *__restrict__ units)
+{
+    const int row = blockIdx.x;
+    const int cnt = row_count[row], u0 = row_unit0[row];
+    for (int k = threadIdx.x; k * ppw < cnt; k += 256)
+        units[u0 + k] = make_int4(row, k * ppw, cnt - k * ppw < ppw ? cnt - k * ppw : ppw, 0);
+}
+
+// After gather_kernel (not inside it: other chunks of the same pixel read
+// n_p at unit setup): one wave per unit (grid-stride) adds add_samples to the
+// counts of the unit's pixels, the same units [0, min(rec[1], max_units)).
+__global__ __launch_bounds__(256) void bump_counts_kernel(int W, const int4 *__restrict__ units,
+                                                          const int *__restrict__ list,
+                                                          const unsigned long long *__restrict__ rec,
+                                                          long long max_units, int add, int *__restrict__ counts)
+{
+    long long n = (long long)rec[1];
+    n = n < max_units ? n : max_units;
+    const int lane = threadIdx.x & 63;
+    for (long long u = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); u < n; u += (long long)gridDim.x * 4) {
+        const int4 e = units[u];
+        if (lane < e.z) {
+            const size_t rowbase = (size_t)e.x * W;
+            counts[rowbase + list[rowbase + e.y + lane]] += add;
         }
     }
 }
@@ -2153,6 +2444,20 @@ struct ptg_context {
     size_t acc2_elems;
     bool moments_pass;  // a pass since the last reset added to d_acc2 ...
     bool plain_pass;    // ... or ran without the flag (d_acc2 then lacks its samples: no noise estimate)
+    // adaptive sampling (ptg_*_active_device), allocated on first use: per slab pixel its sample count, the
+    // over-target bytes, the active list (per slab row, stride W, its active x ascending), per slab row its
+    // active pixels and first unit, the unit table (n_groups entries) and the device record {pixels, units}
+    int32_t *d_counts;
+    uint8_t *d_over;
+    int *d_list, *d_row_count, *d_row_unit0;
+    int4 *d_units;
+    unsigned long long *d_rec;
+    size_t ad_pixels, ad_rows, ad_groups;  // what the buffers above have room for
+    ptg_params list_frame;  // the frame the active list was built for ...
+    bool list_valid;        // ... if any since the last reset
+    bool uniform_pass;      // a ptg_accumulate_device pass since the last reset: no adaptive entry point
+    bool adaptive_pass;     // a ptg_accumulate_active_device pass since the last reset: no uniform n describes the sums
+    long long adaptive_added;  // the adds since the last reset: no count is above their sum
 };
 
 namespace {
@@ -2363,6 +2668,10 @@ int ptg_context_destroy(ptg_context *ctx)
         (void)hipFree(ctx->d_acc2);
     if (ctx->d_sph64)
         (void)hipFree(ctx->d_sph64);
+    for (void *q : {(void *)ctx->d_counts, (void *)ctx->d_over, (void *)ctx->d_list, (void *)ctx->d_row_count,
+                    (void *)ctx->d_row_unit0, (void *)ctx->d_units, (void *)ctx->d_rec})
+        if (q)
+            (void)hipFree(q);
     delete ctx;
     return PTG_OK;
 }
@@ -2379,6 +2688,11 @@ int forget_moments(ptg_context *ctx, hipStream_t stream)
     if (ctx->d_acc2 && ctx->moments_pass)  // (only such passes write to it)
         PTG_HIP(hipMemsetAsync(ctx->d_acc2, 0, ctx->acc2_elems * sizeof(unsigned long long), stream));
     ctx->moments_pass = ctx->plain_pass = false;
+    // the adaptive frame with them: counts zero, no list, no pass of either kind on record
+    if (ctx->d_counts && (ctx->adaptive_pass || ctx->adaptive_added))
+        PTG_HIP(hipMemsetAsync(ctx->d_counts, 0, ctx->ad_pixels * sizeof(int32_t), stream));
+    ctx->list_valid = ctx->uniform_pass = ctx->adaptive_pass = false;
+    ctx->adaptive_added = 0;
     return PTG_OK;
 }
 
@@ -2441,6 +2755,25 @@ int check_moments(const ptg_context *ctx, const KArgs &A, const char *who)
                     std::string(who) + ": a pass since the last reset ran without PTG_FLAG_MOMENTS");
     if (!ctx->d_acc2 || ctx->acc2_elems < acc_elems_for(A) || ctx->acc_elems < acc_elems_for(A))
         return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": the passes were of a smaller frame");
+    return PTG_OK;
+}
+
+// While adaptive passes are in the sums, the pixels hold different numbers of
+// samples: the entry points that take one n for the slab refuse ...
+int refuse_after_adaptive(const ptg_context *ctx, const char *who)
+{
+    if (ctx->adaptive_pass)
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": adaptive passes since the last reset (the pixels "
+                                              "hold different sample counts: use the *_active entry points, or reset)");
+    return PTG_OK;
+}
+
+// ... and the adaptive ones after a uniform pass, which the count slab does not know of
+int refuse_after_uniform(const ptg_context *ctx, const char *who)
+{
+    if (ctx->uniform_pass)
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": a ptg_accumulate_device pass since the last reset "
+                                              "(the sample counts do not describe its sums: reset first)");
     return PTG_OK;
 }
 
@@ -2516,6 +2849,99 @@ int launch_ref64(const ptg_context *ctx, const KArgs &A, double *out64, float *o
     if (blocks > 0)
         ref64::render_kernel<<<(unsigned)blocks, 256, 0, s>>>(R);
     PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int launch_gather(const KArgs &A, int grid, bool count, hipStream_t s, unsigned long long *acc2, const GatherArgs &G)
+{
+    if (grid <= 0)
+        return PTG_OK;
+    const bool bvh = A.n > kLinearMax;
+    const size_t lds = bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
+    switch ((count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0)) {
+    case 0: gather_kernel<false, false, false><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 1: gather_kernel<false, true, false><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 2: gather_kernel<true, false, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    case 3: gather_kernel<true, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    case 4: gather_kernel<false, false, true><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 5: gather_kernel<false, true, true><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 6: gather_kernel<true, false, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    default: gather_kernel<true, true, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    }
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+// The adaptive buffers at the frame's size (allocated on first use; a larger
+// frame replaces them: counts zero, no list)
+int ensure_adaptive(ptg_context *ctx, const KArgs &A, hipStream_t stream)
+{
+    const size_t pixels = (size_t)A.slab_rows * A.W, rows = (size_t)A.slab_rows, groups = (size_t)A.n_groups;
+    if (pixels <= ctx->ad_pixels && rows <= ctx->ad_rows && groups <= ctx->ad_groups)
+        return PTG_OK;
+    if (ctx->adaptive_pass)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "the adaptive passes since the last reset were of a smaller frame");
+    for (void **q : {(void **)&ctx->d_counts, (void **)&ctx->d_over, (void **)&ctx->d_list, (void **)&ctx->d_row_count,
+                     (void **)&ctx->d_row_unit0, (void **)&ctx->d_units, (void **)&ctx->d_rec}) {
+        if (*q)
+            PTG_HIP(hipFree(*q));
+        *q = nullptr;
+    }
+    ctx->ad_pixels = ctx->ad_rows = ctx->ad_groups = 0;
+    ctx->list_valid = false;
+    if (hipMalloc(&ctx->d_counts, pixels * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&ctx->d_over, pixels) != hipSuccess || hipMalloc(&ctx->d_list, pixels * sizeof(int)) != hipSuccess ||
+        hipMalloc(&ctx->d_row_count, rows * sizeof(int)) != hipSuccess ||
+        hipMalloc(&ctx->d_row_unit0, rows * sizeof(int)) != hipSuccess ||
+        hipMalloc(&ctx->d_units, groups * sizeof(int4)) != hipSuccess ||
+        hipMalloc(&ctx->d_rec, 2 * sizeof(unsigned long long)) != hipSuccess)
+        return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the adaptive-sampling buffers failed");
+    PTG_HIP(hipMemsetAsync(ctx->d_counts, 0, pixels * sizeof(int32_t), stream));
+    PTG_HIP(hipMemsetAsync(ctx->d_rec, 0, 2 * sizeof(unsigned long long), stream));
+    ctx->ad_pixels = pixels;
+    ctx->ad_rows = rows;
+    ctx->ad_groups = groups;
+    return PTG_OK;
+}
+
+// the slab geometry of two frames is the same (the active list and the counts are indexed by it)
+bool same_slab(const ptg_params &a, const ptg_params &b)
+{
+    return a.width == b.width && a.height == b.height && a.num_subpixels == b.num_subpixels &&
+           a.band_rows == b.band_rows && a.shard_rank == b.shard_rank && a.shard_count == b.shard_count;
+}
+
+// The adaptive entry points' common start: argument checks done, no uniform
+// pass in the sums, the launch plan's frame fields, both accumulators and the
+// adaptive buffers at the frame's size.
+int begin_adaptive(ptg_context *ctx, const ptg_params *p, KArgs &A, hipStream_t s, const char *who)
+{
+    if (p->flags & PTG_FLAG_REFERENCE_F64)
+        return fail(PTG_ERR_UNSUPPORTED, std::string(who) + ": progressive passes are fp32 only");
+    int rc = refuse_after_uniform(ctx, who), grid = 0;
+    if (rc || (rc = begin_launch(ctx, p, A, grid, s, /*with_acc=*/true)) || (rc = ensure_acc2(ctx, s)))
+        return rc;
+    A.acc = ctx->d_acc;
+    return ensure_adaptive(ctx, A, s);
+}
+
+// List-building steps 2 and 3 after step 1 (list_rows_kernel on `flags`)
+int build_list(ptg_context *ctx, const ptg_params *p, const KArgs &A, const uint8_t *flags, int dilate,
+               unsigned long long *d_info, unsigned long long *d_stats, hipStream_t s)
+{
+    if (A.slab_rows > 0) {
+        list_rows_kernel<<<A.slab_rows, 256, 0, s>>>(A, flags, dilate, ctx->d_list, ctx->d_row_count);
+        PTG_HIP(hipGetLastError());
+    }
+    list_units_kernel<<<1, 256, 0, s>>>(A.slab_rows, A.pixels_per_wave, ctx->d_row_count, ctx->d_row_unit0, ctx->d_rec,
+                                        d_info, d_stats);
+    PTG_HIP(hipGetLastError());
+    if (A.slab_rows > 0) {
+        list_fill_kernel<<<A.slab_rows, 256, 0, s>>>(A.pixels_per_wave, ctx->d_row_count, ctx->d_row_unit0, ctx->d_units);
+        PTG_HIP(hipGetLastError());
+    }
+    ctx->list_frame = *p;
+    ctx->list_valid = true;
     return PTG_OK;
 }
 
@@ -2599,6 +3025,8 @@ int ptg_accumulate_device(ptg_context *ctx, const ptg_params *params, int32_t sa
     if (params->flags & PTG_FLAG_REFERENCE_F64)
         return fail(PTG_ERR_UNSUPPORTED, "progressive passes are fp32 only (the reference-arithmetic mode sums "
                                          "its samples sequentially, main.cpp:192)");
+    if ((rc = refuse_after_adaptive(ctx, "accumulate")))
+        return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
@@ -2612,7 +3040,7 @@ int ptg_accumulate_device(ptg_context *ctx, const ptg_params *params, int32_t sa
     A.segments = d_segments;
     ctx->acc_dirty = true;
     if (grid > 0)  // (an empty pass adds no samples to either accumulator)
-        (moments ? ctx->moments_pass : ctx->plain_pass) = true;
+        (moments ? ctx->moments_pass : ctx->plain_pass) = ctx->uniform_pass = true;
     return launch_render(A, grid, d_segments != nullptr, s, moments ? ctx->d_acc2 : nullptr);
 }
 
@@ -2625,6 +3053,8 @@ int ptg_resolve_device(ptg_context *ctx, const ptg_params *params, int32_t sampl
         return rc;
     if (samples_done < 0 || samples_done > params->samples)
         return fail(PTG_ERR_INVALID_ARGUMENT, "samples_done must be in [0, samples]");
+    if ((rc = refuse_after_adaptive(ctx, "resolve")))
+        return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
@@ -2665,6 +3095,8 @@ int ptg_noise_device(ptg_context *ctx, const ptg_params *params, int32_t samples
         return fail(PTG_ERR_INVALID_ARGUMENT, "noise: samples_done must be in [2, samples]");
     if (!(floor > 0.0) || !(rel_error >= 0.0))
         return fail(PTG_ERR_INVALID_ARGUMENT, "noise: floor must be > 0 and rel_error >= 0");
+    if ((rc = refuse_after_adaptive(ctx, "noise")))
+        return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     KArgs A;
     int grid = 0;
@@ -2703,6 +3135,131 @@ int ptg_read_moments_device(ptg_context *ctx, const ptg_params *params, unsigned
     }
     if (d_sum)
         PTG_HIP(hipMemcpyAsync(d_sum, ctx->d_acc, bytes, hipMemcpyDeviceToDevice, s));
+    return PTG_OK;
+}
+
+int ptg_set_active_mask_device(ptg_context *ctx, const ptg_params *params, const uint8_t *d_mask,
+                               unsigned long long *d_info, void *stream)
+{
+    if (!ctx)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "set_active_mask")))
+        return rc;
+    return build_list(ctx, params, A, d_mask, 0, d_info, nullptr, s);
+}
+
+int ptg_select_active_device(ptg_context *ctx, const ptg_params *params, double rel_error, double floor,
+                             int32_t dilate, float *d_rho, unsigned long long *d_stats, void *stream)
+{
+    if (!ctx)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (!(floor > 0.0) || !(rel_error >= 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "select_active: floor must be > 0 and rel_error >= 0");
+    if (dilate < 0 || dilate > 8)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "select_active: dilate must be in [0, 8]");
+    if (dilate > 0 && params->shard_count > 1)
+        return fail(PTG_ERR_UNSUPPORTED, "select_active: dilate > 0 needs shard_count 1 (the neighbouring rows "
+                                         "live in other shards)");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "select_active")))
+        return rc;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    const long long blocks = (pixels + 255) / 256;  // the kernel strides over the rest
+    select_over_kernel<<<(unsigned)(blocks < kNoiseBlocks ? blocks : kNoiseBlocks), 256, 0, s>>>(
+        A, ctx->d_acc2, ctx->d_counts, rel_error, floor, ctx->d_over, d_rho, d_stats);
+    PTG_HIP(hipGetLastError());
+    return build_list(ctx, params, A, ctx->d_over, dilate, nullptr, d_stats, s);
+}
+
+int ptg_accumulate_active_device(ptg_context *ctx, const ptg_params *params, int32_t add_samples, long long max_units,
+                                 unsigned long long *d_segments, void *stream)
+{
+    if (!ctx)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (add_samples < 0)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "accumulate_active: add_samples must be >= 0");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "accumulate_active")))
+        return rc;
+    if (!ctx->list_valid)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "accumulate_active: no active list since the last reset "
+                                              "(ptg_set_active_mask_device or ptg_select_active_device first)");
+    if (!same_slab(ctx->list_frame, *params))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "accumulate_active: the active list was built for another frame");
+    if (ctx->adaptive_added + add_samples > (1LL << 30))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "accumulate_active: a sample count could pass 2^30 (" +
+                                                  std::to_string(ctx->adaptive_added) + " added since the last reset)");
+    if (add_samples == 0)
+        return PTG_OK;
+    const long long bound = max_units <= 0 || max_units > A.n_groups ? (long long)A.n_groups : max_units;
+    ActivePlan P;
+    if ((rc = plan_active(A.n > kLinearMax, ctx->wave_slots, bound, add_samples, params->chunk_samples, P)))
+        return rc;
+    // the kernel's frame: local samples [0, add_samples) in chunks of P.chunk, every unit accumulates
+    A.sample_begin = 0;
+    A.sample_end = add_samples;
+    plan_single_level(A, P.chunk, add_samples, /*one_shot=*/false);
+    A.n_units = P.n_units;
+    A.segments = d_segments;
+    const GatherArgs G{ctx->d_units, ctx->d_list, ctx->d_counts, ctx->d_rec, bound, P.n_chunks};
+    ctx->acc_dirty = true;
+    ctx->adaptive_pass = ctx->moments_pass = true;
+    ctx->adaptive_added += add_samples;
+    if ((rc = launch_gather(A, P.grid, d_segments != nullptr, s, ctx->d_acc2, G)))
+        return rc;
+    const long long blocks = (bound + 3) / 4;
+    bump_counts_kernel<<<(unsigned)(blocks < kNoiseBlocks ? blocks : kNoiseBlocks), 256, 0, s>>>(
+        A.W, ctx->d_units, ctx->d_list, ctx->d_rec, bound, add_samples, ctx->d_counts);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_resolve_active_device(ptg_context *ctx, const ptg_params *params, float *d_slab, void *stream)
+{
+    if (!ctx || !d_slab)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context or output");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "resolve_active")))
+        return rc;
+    A.out = d_slab;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    if (pixels <= 0)
+        return PTG_OK;
+    resolve_active_kernel<<<(unsigned)((pixels + 255) / 256), 256, 0, s>>>(A, ctx->d_counts);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_read_sample_counts_device(ptg_context *ctx, const ptg_params *params, int32_t *d_counts, void *stream)
+{
+    if (!ctx || !d_counts)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context or output");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "read_sample_counts")))
+        return rc;
+    PTG_HIP(hipMemcpyAsync(d_counts, ctx->d_counts, (size_t)A.slab_rows * A.W * sizeof(int32_t),
+                           hipMemcpyDeviceToDevice, s));
     return PTG_OK;
 }
 
@@ -2952,6 +3509,119 @@ int ptg_render_to_noise(const ptg_sphere *spheres, size_t n_spheres, const ptg_c
         double *dst = image_rgb + (size_t)j * W * 3;
         for (int i = 0; i < W * 3; ++i)  // main.cpp:196: image[row] += ...
             dst[i] = dst[i] + (double)host[(size_t)j * W * 3 + i];
+    }
+    if (report)
+        *report = rep;
+    return PTG_OK;
+}
+
+int ptg_render_adaptive(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
+                        int device, const ptg_adaptive_target *target, double *image_rgb, int32_t *sample_counts,
+                        ptg_adaptive_report *report)
+{
+    if (!image_rgb || !target)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: NULL image or target");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (!(target->floor > 0.0) || !(target->rel_error >= 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: floor must be > 0 and rel_error >= 0");
+    if (!(target->max_fraction >= 0.0 && target->max_fraction < 1.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: max_fraction must be in [0, 1)");
+    if (target->dilate < 0 || target->dilate > 8)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: dilate must be in [0, 8]");
+    if (params->shard_count != 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: shard_count must be 1 (one device decides for "
+                                              "the whole frame)");
+    if (params->flags & PTG_FLAG_REFERENCE_F64)
+        return fail(PTG_ERR_UNSUPPORTED, "render_adaptive: progressive passes are fp32 only");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    if ((rc = ptg_noise_schedule(target->min_samples, params->samples, ends, PTG_NOISE_MAX_PASSES, &n_ends)))
+        return rc;
+    ptg_adaptive_report rep{};
+    ptg_context *ctx = nullptr;
+    if ((rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx)))
+        return rc;
+    const ptg_params &p = *params;
+    const int W = p.width, H = p.height;
+    const int slab_rows = shard_slab_rows(H, p.band_rows, 1);
+    const size_t slab_pixels = (size_t)slab_rows * W;
+    const bool count = (p.flags & (PTG_FLAG_COUNT_TESTS | PTG_FLAG_COUNT_NONFINITE)) != 0;
+    std::vector<float> host(slab_pixels * 3);
+    std::vector<int32_t> host_counts(sample_counts ? slab_pixels : 0);
+    float *d_slab = nullptr;
+    int32_t *d_cnt = nullptr;
+    unsigned long long *d_stats = nullptr;  // 6 statistics, then the 4 kernel counters
+    // everything on the null stream, in order; each selection's 48 bytes copied back synchronously
+    auto run = [&]() -> int {
+        int r;
+        if (hipMalloc(&d_slab, slab_pixels * 3 * sizeof(float)) != hipSuccess ||
+            hipMalloc(&d_stats, 10 * sizeof(unsigned long long)) != hipSuccess ||
+            (sample_counts && hipMalloc(&d_cnt, slab_pixels * sizeof(int32_t)) != hipSuccess))
+            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the image slab failed");
+        PTG_HIP(hipMemsetAsync(d_stats, 0, 10 * sizeof(unsigned long long), nullptr));
+        unsigned long long *d_seg = count ? d_stats + 6 : nullptr;
+        if ((r = ptg_reset_accumulation_device(ctx, &p, nullptr)) ||
+            (r = ptg_set_active_mask_device(ctx, &p, nullptr, nullptr, nullptr)))  // pass 0: every pixel
+            return r;
+        unsigned long long active = (unsigned long long)W * H;
+        long long units = 0;  // pass 0: the host-side bound
+        int32_t done = 0;
+        for (int k = 0; k < n_ends; ++k) {
+            unsigned long long st[6] = {0, 0, 0, 0, 0, 0};
+            PTG_HIP(hipMemsetAsync(d_stats, 0, sizeof(st), nullptr));
+            const int32_t add = ends[k] - done;
+            if ((r = ptg_accumulate_active_device(ctx, &p, add, units, d_seg, nullptr)))
+                return r;
+            done = ends[k];
+            rep.total_samples += active * (unsigned long long)add;
+            if ((r = ptg_select_active_device(ctx, &p, target->rel_error, target->floor, target->dilate, nullptr,
+                                              d_stats, nullptr)))
+                return r;
+            PTG_HIP(hipMemcpy(st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
+            rep.passes = k + 1;
+            rep.max_samples = done;
+            rep.pixels = st[3];
+            rep.pixels_over = st[0];
+            rep.pass_added[k] = add;
+            rep.pass_over[k] = st[0];
+            rep.pass_active[k] = st[4];
+            const uint32_t max_bits = (uint32_t)st[2];
+            float max_rho;
+            std::memcpy(&max_rho, &max_bits, sizeof(max_rho));
+            rep.max_rho = (double)max_rho;
+            rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
+            rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
+            if (rep.converged)
+                break;
+            active = st[4];
+            units = (long long)st[5];  // (> 0: a pixel over the target is active)
+        }
+        if ((r = ptg_resolve_active_device(ctx, &p, d_slab, nullptr)))
+            return r;
+        if (sample_counts) {
+            if ((r = ptg_read_sample_counts_device(ctx, &p, d_cnt, nullptr)))
+                return r;
+            PTG_HIP(hipMemcpy(host_counts.data(), d_cnt, slab_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+        if (count)
+            PTG_HIP(hipMemcpy(rep.counters, d_stats + 6, sizeof(rep.counters), hipMemcpyDeviceToHost));
+        PTG_HIP(hipMemcpy(host.data(), d_slab, slab_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        return PTG_OK;
+    };
+    rc = run();
+    for (void *q : {(void *)d_slab, (void *)d_stats, (void *)d_cnt})
+        if (q)
+            (void)hipFree(q);
+    ptg_context_destroy(ctx);
+    if (rc)
+        return rc;
+    for (int j = 0; j < H; ++j) {  // shard_count 1: slab row j is output row j
+        double *dst = image_rgb + (size_t)j * W * 3;
+        for (int i = 0; i < W * 3; ++i)  // main.cpp:196: image[row] += ...
+            dst[i] = dst[i] + (double)host[(size_t)j * W * 3 + i];
+        if (sample_counts)
+            std::memcpy(sample_counts + (size_t)j * W, host_counts.data() + (size_t)j * W, (size_t)W * sizeof(int32_t));
     }
     if (report)
         *report = rep;

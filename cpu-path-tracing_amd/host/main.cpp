@@ -6,7 +6,8 @@
 //   pt_render_gpu [--spp N] [--scene NAME|FILE] [--width W] [--height H] [--seed S]
 //                 [--devices 0,1,...] [--out FILE] [--format p3|p6]
 //                 [--save-scene FILE] [--dump-json FILE] [--no-render] [--exact-math]
-//                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]]
+//                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]
+//                  [--adaptive [--dilate D] [--spp-map FILE]]]
 //
 //   spp      total samples per pixel (main.cpp:206: divided by the 4 sub-pixels), default 4
 //   scene    box_mirror (the reference binary's scene, main.cpp:25,208) | box | simple |
@@ -25,6 +26,12 @@
 //            standard error above R, relative to max(pixel mean, F) (default 0.01).  The
 //            image equals a plain run's at the spp the "noise:" line on stderr reports.
 //            One device only (a --devices list of several: exit status 2).
+//   --adaptive  with --noise-target (exit status 2 without): after the first pass only the
+//            pixels still above R, or within D pixels (--dilate, default 1, 0..8) of one, get
+//            the later passes (ptg_render_adaptive); a pixel's value equals a plain run's at
+//            its own spp.  --spp-map FILE writes the samples per sub-pixel of every pixel as
+//            a binary PGM (P5; 16-bit big-endian values when a count is above 255).  The
+//            "noise:" line then ends with the mean samples per sub-pixel.
 //   --save-scene / --dump-json write the scene (scene file) / the scene and the
 //            camera::with_config result (JSON, 17 digits) and need no GPU with --no-render
 #include <chrono>
@@ -115,8 +122,9 @@ int main(int argc, char *argv[])
     std::uint64_t seed = pt::gpu::default_seed;
     bool render = true;
     int flags = 0;
-    bool to_noise = false;
-    int min_spp = 64;
+    bool to_noise = false, adaptive = false;
+    int min_spp = 64, dilate = 1;
+    std::string spp_map;
     ptg_noise_target target{};
     target.floor = 0.01;
     target.max_fraction = 0.01;
@@ -173,6 +181,12 @@ int main(int argc, char *argv[])
                 target.max_fraction = std::atof(val().c_str());
             else if (a == "--min-spp")
                 min_spp = std::atoi(val().c_str());
+            else if (a == "--adaptive")
+                adaptive = true;
+            else if (a == "--dilate")
+                dilate = std::atoi(val().c_str());
+            else if (a == "--spp-map")
+                spp_map = val();
             else {
                 std::fprintf(stderr, "unknown option %s\n", a.c_str());
                 return 2;
@@ -181,6 +195,10 @@ int main(int argc, char *argv[])
     }
     if (width <= 0 || height <= 0 || spp < 0 || (format != "p3" && format != "p6")) {
         std::fprintf(stderr, "bad width/height/spp/format\n");
+        return 2;
+    }
+    if ((adaptive && !to_noise) || (!spp_map.empty() && !adaptive)) {
+        std::fprintf(stderr, "--adaptive needs --noise-target, --spp-map needs --adaptive\n");
         return 2;
     }
     int const samps = spp / (num_subpixels * num_subpixels);
@@ -213,17 +231,48 @@ int main(int argc, char *argv[])
             return 2;
         }
         target.min_samples = min_spp / (num_subpixels * num_subpixels);
-        ptg_noise_report rep{};
-        rc = pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep, num_subpixels,
-                                            seed, devs[0], flags);
-        if (rc == PTG_OK) {
-            samps_done = rep.samples_done;
-            std::fprintf(stderr,
-                         "noise: stopped at %d spp after %d passes, %llu/%llu pixels above %g, max %g, mean %g, "
-                         "converged %d\n",
-                         samps_done * num_subpixels * num_subpixels, rep.passes,
-                         static_cast<unsigned long long>(rep.pixels_over), static_cast<unsigned long long>(rep.pixels),
-                         target.rel_error, rep.max_rho, rep.mean_rho, rep.converged);
+        if (adaptive) {
+            ptg_adaptive_target const at{target.rel_error, target.floor, target.max_fraction, target.min_samples, dilate};
+            ptg_adaptive_report rep{};
+            std::vector<std::int32_t> counts;
+            rc = pt::gpu::render_image_adaptive(some_scene, cam, image, width, height, samps, at, rep,
+                                                spp_map.empty() ? nullptr : &counts, num_subpixels, seed, devs[0],
+                                                flags);
+            if (rc == PTG_OK) {
+                samps_done = rep.max_samples;
+                double const mean = rep.pixels ? double(rep.total_samples) / double(rep.pixels) : 0.0;
+                std::fprintf(stderr,
+                             "noise: adaptive, at most %d spp after %d passes, %llu/%llu pixels above %g, max %g, "
+                             "mean %g, converged %d, mean samples per sub-pixel %g\n",
+                             samps_done * num_subpixels * num_subpixels, rep.passes,
+                             static_cast<unsigned long long>(rep.pixels_over),
+                             static_cast<unsigned long long>(rep.pixels), target.rel_error, rep.max_rho, rep.mean_rho,
+                             rep.converged, mean);
+                if (!spp_map.empty()) {
+                    bool const wide = rep.max_samples > 255;
+                    std::ofstream m{spp_map, std::ios::binary};
+                    m << "P5\n" << width << ' ' << height << '\n' << (wide ? 65535 : 255) << '\n';
+                    for (std::int32_t c : counts) {
+                        int const v = c < 0 ? 0 : (c > 65535 ? 65535 : c);
+                        if (wide)
+                            m.put(static_cast<char>(v >> 8));
+                        m.put(static_cast<char>(v & 255));
+                    }
+                }
+            }
+        } else {
+            ptg_noise_report rep{};
+            rc = pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep, num_subpixels,
+                                                seed, devs[0], flags);
+            if (rc == PTG_OK) {
+                samps_done = rep.samples_done;
+                std::fprintf(stderr,
+                             "noise: stopped at %d spp after %d passes, %llu/%llu pixels above %g, max %g, mean %g, "
+                             "converged %d\n",
+                             samps_done * num_subpixels * num_subpixels, rep.passes,
+                             static_cast<unsigned long long>(rep.pixels_over), static_cast<unsigned long long>(rep.pixels),
+                             target.rel_error, rep.max_rho, rep.mean_rho, rep.converged);
+            }
         }
     } else if (nd == 1 && devs[0] < 0) {  // main.cpp:214-236 replaced by one call
         rc = pt::gpu::render_image(some_scene, cam, image, width, height, samps, num_subpixels, seed, -1, flags);

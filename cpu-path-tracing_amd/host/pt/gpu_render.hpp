@@ -85,5 +85,34 @@ inline int render_image_to_noise(scene const &scn, camera const &cam, std::vecto
                                reinterpret_cast<double *>(image.data()), &report);
 }
 
+// render_image_to_noise whose later passes sample only the pixels still over the
+// target or within target.dilate pixels of one (ptg_render_adaptive): a pixel's
+// value equals render_image's at samps = its own count.  sample_counts
+// (optional) receives width * height counts in the image's row order.
+inline int render_image_adaptive(scene const &scn, camera const &cam, std::vector<vec3> &image, int width, int height,
+                                 int samps, ptg_adaptive_target const &target, ptg_adaptive_report &report,
+                                 std::vector<std::int32_t> *sample_counts = nullptr, int num_subpixels = 2,
+                                 std::uint64_t seed = default_seed, int device = -1, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    if (sample_counts)
+        sample_counts->assign(image.size(), 0);
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return ptg_render_adaptive(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                               reinterpret_cast<ptg_camera const *>(&cam), &p, device, &target,
+                               reinterpret_cast<double *>(image.data()),
+                               sample_counts ? sample_counts->data() : nullptr, &report);
+}
+
 }  // namespace gpu
 }  // namespace pt

@@ -24,6 +24,8 @@ EXPORTS = (
     "ptg_multi_frame_timing", "ptg_multi_image", "ptg_math_probe_device", "ptg_multi_comm_info",
     "ptg_device_pci_bus_id", "ptg_launch_info",
     "ptg_noise_device", "ptg_read_moments_device", "ptg_noise_schedule", "ptg_render_to_noise",
+    "ptg_set_active_mask_device", "ptg_select_active_device", "ptg_accumulate_active_device",
+    "ptg_resolve_active_device", "ptg_read_sample_counts_device", "ptg_render_adaptive",
 )
 
 
@@ -56,6 +58,22 @@ class NoiseReport(C.Structure):  # ptg_noise_report
 
 
 assert C.sizeof(NoiseTarget) == 32 and C.sizeof(NoiseReport) == 48 + 12 * NOISE_MAX_PASSES
+
+
+class AdaptiveTarget(C.Structure):  # ptg_adaptive_target
+    _fields_ = [("rel_error", C.c_double), ("floor", C.c_double), ("max_fraction", C.c_double),
+                ("min_samples", C.c_int32), ("dilate", C.c_int32)]
+
+
+class AdaptiveReport(C.Structure):  # ptg_adaptive_report
+    _fields_ = [("passes", C.c_int32), ("converged", C.c_int32), ("max_samples", C.c_int32),
+                ("reserved_", C.c_int32), ("pixels", C.c_uint64), ("pixels_over", C.c_uint64),
+                ("max_rho", C.c_double), ("mean_rho", C.c_double), ("total_samples", C.c_uint64),
+                ("counters", C.c_uint64 * 4), ("pass_added", C.c_int32 * NOISE_MAX_PASSES),
+                ("pass_over", C.c_uint64 * NOISE_MAX_PASSES), ("pass_active", C.c_uint64 * NOISE_MAX_PASSES)]
+
+
+assert C.sizeof(AdaptiveTarget) == 32 and C.sizeof(AdaptiveReport) == 88 + 20 * NOISE_MAX_PASSES
 
 _lib = None
 
@@ -104,6 +122,13 @@ def lib():
             "ptg_noise_schedule": (I, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
             "ptg_render_to_noise": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(NoiseTarget), P,
                                         C.POINTER(NoiseReport)]),
+            "ptg_set_active_mask_device": (I, [P, C.POINTER(Params), P, P, P]),
+            "ptg_select_active_device": (I, [P, C.POINTER(Params), C.c_double, C.c_double, C.c_int32, P, P, P]),
+            "ptg_accumulate_active_device": (I, [P, C.POINTER(Params), C.c_int32, C.c_longlong, P, P]),
+            "ptg_resolve_active_device": (I, [P, C.POINTER(Params), P, P]),
+            "ptg_read_sample_counts_device": (I, [P, C.POINTER(Params), P, P]),
+            "ptg_render_adaptive": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(AdaptiveTarget), P, P,
+                                        C.POINTER(AdaptiveReport)]),
             "ptg_multi_inject_gather_fault_": (I, [P, I]),
             # internal (tests): n shards on one device, gathered by device copies
             "ptg_multi_create_local_": (I, [P, C.c_size_t, P, I, I, C.POINTER(C.c_void_p)]),

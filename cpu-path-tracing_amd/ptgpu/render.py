@@ -4,6 +4,9 @@
                             (main.cpp:214-236): fills the caller's image
                             (H*W RGB doubles, reference row order) exactly as
                             the loop would, through ptg_render.
+* render_to_noise(...),  -- render() that stops when a noise target is met;
+  render_adaptive(...)      the adaptive one gives the later passes only to
+                            the pixels still over it (a sample count per pixel).
 * Context                -- device-resident scene for repeated renders into
                             torch CUDA tensors (bench, multi-GPU).
 * render_sharded(...)    -- one process per GPU: each rank renders its
@@ -19,7 +22,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from ._abi import NOISE_MAX_PASSES, NoiseReport, NoiseTarget, Params, check, lib
+from ._abi import NOISE_MAX_PASSES, AdaptiveReport, AdaptiveTarget, NoiseReport, NoiseTarget, Params, check, lib
 from .scene import CAMERA_DT, SPHERE_DT, camera, scene
 
 DEFAULT_SEED = 0x5EED0001
@@ -137,6 +140,41 @@ def render_to_noise(scn, cam, image: np.ndarray, width: int, height: int, sample
     return {"samples_done": rep.samples_done, "passes": rep.passes, "converged": rep.converged,
             "pixels": rep.pixels, "pixels_over": rep.pixels_over, "max_rho": rep.max_rho, "mean_rho": rep.mean_rho,
             "pass_samples": list(rep.pass_samples[:rep.passes]), "pass_over": list(rep.pass_over[:rep.passes])}
+
+
+def render_adaptive(scn, cam, image: np.ndarray, width: int, height: int, samples: int, rel_error: float,
+                    floor: float = 0.01, max_fraction: float = 0.01, min_samples: int = 16, dilate: int = 1,
+                    num_subpixels: int = 2, seed: int = DEFAULT_SEED, device: int = -1, flags: int = 0,
+                    sample_counts: bool = False):
+    """ptg_render_adaptive: render_to_noise() whose later passes sample only
+    the pixels still over the target, or within `dilate` pixels of one that
+    is.  A pixel's value equals render()'s at samples = its own count bit for
+    bit.  Returns the report (passes, converged, max_samples, pixels,
+    pixels_over, max_rho, mean_rho, total_samples = the sum of the pixels'
+    counts, mean_samples, counters, and per pass: pass_added, pass_over,
+    pass_active); with sample_counts=True returns (report, counts) with
+    counts the int32 [height, width] samples per sub-pixel of every pixel,
+    in the image's row order."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    if image.dtype != np.float64 or not image.flags["C_CONTIGUOUS"] or image.size != width * height * 3:
+        raise ValueError("image must be a C-contiguous float64 array of width*height*3 values")
+    p = make_params(width, height, samples, num_subpixels, seed, flags=flags)
+    target = AdaptiveTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), int(dilate))
+    rep = AdaptiveReport()
+    counts = np.zeros((height, width), dtype=np.int32) if sample_counts else None
+    check(lib().ptg_render_adaptive(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
+                                    C.byref(p), int(device), C.byref(target), image.ctypes.data_as(C.c_void_p),
+                                    counts.ctypes.data_as(C.c_void_p) if sample_counts else None, C.byref(rep)),
+          "ptg_render_adaptive")
+    n = rep.passes
+    out = {"passes": n, "converged": rep.converged, "max_samples": rep.max_samples, "pixels": rep.pixels,
+           "pixels_over": rep.pixels_over, "max_rho": rep.max_rho, "mean_rho": rep.mean_rho,
+           "total_samples": rep.total_samples,
+           "mean_samples": rep.total_samples / rep.pixels if rep.pixels else 0.0,
+           "counters": list(rep.counters), "pass_added": list(rep.pass_added[:n]),
+           "pass_over": list(rep.pass_over[:n]), "pass_active": list(rep.pass_active[:n])}
+    return (out, counts) if sample_counts else out
 
 
 def render_multi(scn, cam, image: np.ndarray, width: int, height: int, samples: int, devices,
@@ -432,6 +470,65 @@ class Context:
         s = self._stream(stream)
         check(lib().ptg_read_moments_device(self._h, C.byref(params), ptr(sums), ptr(sumsq), C.c_void_p(s)),
               "ptg_read_moments_device")
+
+    # ---- adaptive sampling (ptg_*_active_device): later passes only where the image is still noisy
+    def _pixels(self, params: Params) -> int:
+        return shard_rows(params.height, params.band_rows, params.shard_count) * params.width
+
+    def set_active_mask(self, params: Params, mask=None, info=None, stream=None) -> None:
+        """The active list from `mask` (uint8, slab rows*W: != 0 is active;
+        None: every pixel of the image).  `info` (int64 [2], optional)
+        receives the active pixels and the active work units."""
+        import torch
+        if mask is not None:
+            self._check(mask, torch.uint8, self._pixels(params))
+        if info is not None:
+            self._check(info, torch.int64, 2)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().ptg_set_active_mask_device(self._h, C.byref(params), ptr(mask), ptr(info),
+                                               C.c_void_p(self._stream(stream))), "ptg_set_active_mask_device")
+
+    def select_active(self, params: Params, rel_error: float, floor: float, dilate: int = 0, rho=None, stats=None,
+                      stream=None) -> None:
+        """The active list from the noise of the samples so far, each pixel
+        with its own count: active = within `dilate` pixels of a pixel whose
+        rho > rel_error.  `rho` (float32, slab rows*W) and `stats` (int64 [6],
+        zeroed by the caller: noise()'s four, += active pixels, += active
+        units) are optional."""
+        import torch
+        if rho is not None:
+            self._check(rho, torch.float32, self._pixels(params))
+        if stats is not None:
+            self._check(stats, torch.int64, 6)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().ptg_select_active_device(self._h, C.byref(params), float(rel_error), float(floor), int(dilate),
+                                             ptr(rho), ptr(stats), C.c_void_p(self._stream(stream))),
+              "ptg_select_active_device")
+
+    def accumulate_active(self, params: Params, add_samples: int, max_units: int = 0, segments=None,
+                          stream=None) -> None:
+        """The next `add_samples` samples of every pixel of the active list
+        (max_units: the unit count read back from stats[5] / info[1], or 0)."""
+        import torch
+        if segments is not None:
+            self._check(segments, torch.int64, _n_counters(params.flags))
+        check(lib().ptg_accumulate_active_device(self._h, C.byref(params), int(add_samples), int(max_units),
+                                                 C.c_void_p(segments.data_ptr()) if segments is not None else None,
+                                                 C.c_void_p(self._stream(stream))), "ptg_accumulate_active_device")
+
+    def resolve_active(self, out, params: Params, stream=None) -> None:
+        """The image of the samples so far, each pixel averaged over its own count."""
+        import torch
+        self._check(out, torch.float32, self._pixels(params) * 3)
+        check(lib().ptg_resolve_active_device(self._h, C.byref(params), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(self._stream(stream))), "ptg_resolve_active_device")
+
+    def read_sample_counts(self, params: Params, counts, stream=None) -> None:
+        """The samples per sub-pixel every pixel holds (int32, slab rows*W)."""
+        import torch
+        self._check(counts, torch.int32, self._pixels(params))
+        check(lib().ptg_read_sample_counts_device(self._h, C.byref(params), C.c_void_p(counts.data_ptr()),
+                                                  C.c_void_p(self._stream(stream))), "ptg_read_sample_counts_device")
 
     def trace_samples(self, coords, params: Params):
         """Parity probe: radiance + segment count of individual paths

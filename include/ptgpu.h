@@ -246,7 +246,11 @@ int ptg_render_device(ptg_context *ctx, const ptg_params *params, float *d_slab,
  * a resolve turns the sums so far into an image (clamped means over
  * samples_done samples) without consuming them.  After passes that together
  * cover samples [0, params->samples), ptg_resolve_device(..., samples, ...)
- * equals ptg_render_device bit for bit.  Reset before a new frame. */
+ * equals ptg_render_device bit for bit.  Reset before a new frame.
+ * After ptg_accumulate_active_device passes ("adaptive sampling" below) the
+ * pixels hold different sample counts: ptg_accumulate_device,
+ * ptg_resolve_device and ptg_noise_device then return
+ * PTG_ERR_INVALID_ARGUMENT until the next reset. */
 int ptg_reset_accumulation_device(ptg_context *ctx, const ptg_params *params, void *stream);
 int ptg_accumulate_device(ptg_context *ctx, const ptg_params *params, int32_t sample_begin, int32_t sample_end,
                           unsigned long long *d_segments, void *stream);
@@ -325,6 +329,100 @@ typedef struct ptg_noise_report {
 int ptg_render_to_noise(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
                         const ptg_params *params, int device, const ptg_noise_target *target, double *image_rgb,
                         ptg_noise_report *report);
+
+/* ---- adaptive sampling (DESIGN.md "adaptive sampling") ------------------
+ * Later passes only for the pixels still noisy.  The context keeps, beside
+ * the two accumulators, an int32 sample count n_p per slab pixel (allocated on
+ * first use, zeroed by ptg_reset_accumulation_device) and an active list.
+ * The guarantee: after any sequence of the calls below, pixel p holds exactly
+ * samples [0, n_p) of each of its sub-pixels -- S1 and S2 are the sums over
+ * those samples, and its resolved value equals ptg_render_device's at
+ * samples = n_p bit for bit, whatever the chunking, the sharding (dilate 0)
+ * or the grouping of the active pixels into work units.
+ * All asynchronous on stream; slabs in slab-row order, like d_rho.  While
+ * adaptive passes are in the sums (until the next reset),
+ * ptg_accumulate_device, ptg_resolve_device and ptg_noise_device return
+ * PTG_ERR_INVALID_ARGUMENT (their one n no longer describes the sums), and
+ * the entry points below do after a ptg_accumulate_device pass;
+ * ptg_read_moments_device keeps working (adaptive passes always sum both
+ * moments; PTG_FLAG_MOMENTS is not needed).
+ *
+ * ptg_set_active_mask_device: the active list from a byte mask (also the
+ * region-of-interest entry point): pixel (slab_row, x) is active when
+ * d_mask[slab_row * width + x] != 0; d_mask NULL: every pixel of the image.
+ * d_info (optional) receives 2 values: active pixels, active work units (a
+ * slab row's active pixels in ascending x, cut into units of 64 /
+ * num_subpixels^2 pixels; units never span rows).
+ *
+ * ptg_select_active_device: rho as ptg_noise_device defines it, with each
+ * pixel's own n_p in place of samples_done (n_p < 2: rho = +inf).  A pixel is
+ * over when rho > rel_error, and active when some pixel of its
+ * (2 dilate + 1)^2 window, clipped to the image, is over.  dilate in [0, 8];
+ * dilate > 0 with shard_count > 1 is PTG_ERR_UNSUPPORTED (the neighbouring
+ * rows live in other shards).  d_rho optional.  d_stats (optional): 6 uint64
+ * the caller zeroes, [0]..[3] as ptg_noise_device's (so [0] counts the pixels
+ * over, not the pixels active), [4] += active pixels, [5] += active units.
+ * floor > 0 and rel_error >= 0, as there.
+ *
+ * ptg_accumulate_active_device: every pixel of the active list receives its
+ * next add_samples samples [n_p, n_p + add_samples), summed into S1 and S2,
+ * and its count rises by add_samples.  max_units <= 0: the launch is sized
+ * for the most units the slab can hold; a caller that read the unit count
+ * back ([5] or d_info[1]) passes it, and a sparse list launches a small grid
+ * (the kernel takes the true count from the device; units past max_units are
+ * left out of the pass, neither sampled nor counted).  An empty list does no
+ * work and is not an error.  PTG_ERR_INVALID_ARGUMENT when add_samples < 0,
+ * without an active list since the last reset, with a list built for another
+ * frame geometry, or when the adds since the last reset would pass 2^30.
+ * d_segments as ptg_accumulate_device's.
+ *
+ * ptg_resolve_active_device: ptg_resolve_device's arithmetic with each
+ * pixel's own n_p (n_p = 0: 0); the sums are kept.
+ * ptg_read_sample_counts_device: the counts, slab_rows * width int32. */
+int ptg_set_active_mask_device(ptg_context *ctx, const ptg_params *params, const uint8_t *d_mask,
+                               unsigned long long *d_info, void *stream);
+int ptg_select_active_device(ptg_context *ctx, const ptg_params *params, double rel_error, double floor,
+                             int32_t dilate, float *d_rho, unsigned long long *d_stats, void *stream);
+int ptg_accumulate_active_device(ptg_context *ctx, const ptg_params *params, int32_t add_samples, long long max_units,
+                                 unsigned long long *d_segments, void *stream);
+int ptg_resolve_active_device(ptg_context *ctx, const ptg_params *params, float *d_slab, void *stream);
+int ptg_read_sample_counts_device(ptg_context *ctx, const ptg_params *params, int32_t *d_counts, void *stream);
+
+typedef struct ptg_adaptive_target {
+    double rel_error;    /* a pixel is over the target when rho > rel_error (>= 0) */
+    double floor;        /* rho's denominator is max(pixel mean, floor) (> 0) */
+    double max_fraction; /* stop when at most this fraction of the pixels is over; in [0, 1) */
+    int32_t min_samples; /* every pixel gets this many samples per sub-pixel before the first check (>= 2) */
+    int32_t dilate;      /* a pixel stays active while a pixel of its (2 dilate + 1)^2 window is over; 0..8 */
+} ptg_adaptive_target;
+
+typedef struct ptg_adaptive_report {
+    int32_t passes;
+    int32_t converged;    /* the last check met the target */
+    int32_t max_samples;  /* the largest sample count per sub-pixel: the last pass's end */
+    int32_t reserved_;
+    uint64_t pixels;
+    uint64_t pixels_over; /* of the last check */
+    double max_rho, mean_rho; /* of the last check, as ptg_noise_report's (+inf counts as 4096 in the mean) */
+    uint64_t total_samples;   /* sum over the pixels of n_p (samples per sub-pixel) */
+    uint64_t counters[4];     /* ptg_render_device's d_segments counters, with PTG_FLAG_COUNT_TESTS (else 0) */
+    int32_t pass_added[PTG_NOISE_MAX_PASSES];   /* samples pass k added to each of its active pixels */
+    uint64_t pass_over[PTG_NOISE_MAX_PASSES];   /* pixels over the target after pass k */
+    uint64_t pass_active[PTG_NOISE_MAX_PASSES]; /* pixels active after pass k (over, dilated) */
+} ptg_adaptive_report;
+
+/* ptg_render_to_noise with adaptive passes.  Synchronous; shard_count must be
+ * 1.  With e_0 < e_1 < ... the ends of ptg_noise_schedule(target->min_samples,
+ * params->samples): pass 0 gives every pixel e_0 samples; after each pass one
+ * ptg_select_active_device (48 bytes copied back); it stops when pixels over
+ * <= max_fraction * pixels or at the last end; otherwise the active pixels
+ * get e_(k+1) - e_k more samples.  Then resolves and ADDS into image_rgb like
+ * the drop-in entry point; a pixel's value equals that entry point's at
+ * samples = its count bit for bit.  sample_counts (optional): width * height
+ * int32 in the reference's row order; report optional. */
+int ptg_render_adaptive(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                        const ptg_params *params, int device, const ptg_adaptive_target *target, double *image_rgb,
+                        int32_t *sample_counts, ptg_adaptive_report *report);
 
 /* Reassemble shard_count gathered slabs (rank-major, as all-gather lays them
  * out) into the width*height*3 image. */
