@@ -20,7 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cstdint>
+#include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
@@ -46,7 +49,18 @@ struct Shard {
     unsigned long long *counters = nullptr;  // PTG_FLAG_COUNT_TESTS: 4 per shard
     ncclComm_t comm = nullptr;
     bool stuck = false;  // destroy(): a broken group's stream did not drain
+    // noise-target and adaptive frames (reserve_adaptive): this shard's over
+    // bytes (also the staging of a host mask), every shard's after the
+    // all-gather (rank-major), the 6 statistics + 4 kernel counters, the
+    // sample counts read back
+    uint8_t *over = nullptr, *over_all = nullptr;
+    unsigned long long *stats = nullptr;
+    int32_t *cnt = nullptr;
+    size_t ad_pixels = 0;  // slab pixels the four are sized for
+    long long max_units = 0;  // the active units of the last select (0: the host-side bound)
 };
+
+constexpr int kStats = 10;  // per shard: 6 statistics, then 4 kernel counters
 
 // Restores the calling thread's current HIP device on every return path.
 struct DeviceGuard {
@@ -96,6 +110,11 @@ struct ptg_multi {
     // context refuses further frames (PTG_ERR_HIP) until destroyed
     bool broken = false;
     int inject_gather_fault = -1;  // tests: fail ncclGather at this shard
+    // noise-target and adaptive frames: every shard's statistics land here
+    // (pinned, kStats per shard) with one synchronisation per pass
+    unsigned long long *host_stats = nullptr;
+    std::vector<uint8_t> host_mask;
+    std::vector<int32_t> host_cnt;
 };
 
 namespace {
@@ -148,6 +167,9 @@ int destroy(ptg_multi *m)
             (void)hipFree(s.slab);
         if (s.counters)
             (void)hipFree(s.counters);
+        for (void *q : {(void *)s.over, (void *)s.over_all, (void *)s.stats, (void *)s.cnt})
+            if (q)
+                (void)hipFree(q);
         if (s.done)
             (void)hipEventDestroy(s.done);
         if (s.t_begin)
@@ -168,6 +190,8 @@ int destroy(ptg_multi *m)
         if (m->t_unsharded)
             (void)hipEventDestroy(m->t_unsharded);
     }
+    if (!any_stuck && m->host_stats)
+        (void)hipHostFree(m->host_stats);
     delete m;
     return rc == PTG_OK ? PTG_OK : fail(rc, "multi: a broken group's stream did not drain within 10 s; its buffers were leaked");
 }
@@ -231,13 +255,10 @@ int create(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, c
     return PTG_OK;
 }
 
-int check_frame(const ptg_multi *m, const ptg_params *p)
+// the part of check_frame that needs no context (the one-shot wrappers check
+// their arguments before they create one)
+int check_frame_params(const ptg_params *p)
 {
-    if (!m || !p)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "multi: NULL context or params");
-    if (m->broken)
-        return fail(PTG_ERR_HIP, "multi: the context's RCCL group failed earlier and its communicators were "
-                                 "aborted; destroy it");
     if (p->width <= 0 || p->height <= 0 || p->band_rows < 1)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi: width, height and band_rows must be positive");
     if (p->shard_count != 1 || p->shard_rank != 0)
@@ -246,6 +267,16 @@ int check_frame(const ptg_multi *m, const ptg_params *p)
         return fail(PTG_ERR_UNSUPPORTED, "render_multi renders the fp32 kernel only (the reference-arithmetic "
                                          "mode keeps doubles: use ptg_render)");
     return PTG_OK;
+}
+
+int check_frame(const ptg_multi *m, const ptg_params *p)
+{
+    if (!m || !p)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi: NULL context or params");
+    if (m->broken)
+        return fail(PTG_ERR_HIP, "multi: the context's RCCL group failed earlier and its communicators were "
+                                 "aborted; destroy it");
+    return check_frame_params(p);
 }
 
 // params of shard k
@@ -307,6 +338,47 @@ int reserve(ptg_multi *m, const ptg_params *p, size_t &slab_elems)
     return PTG_OK;
 }
 
+// One RCCL group over the shards: call(k, shard) queues shard k's collective
+// (`what` names it in the error).  Every device is made current once BEFORE
+// the group opens, so that inside it only the collective calls can fail; the
+// group is closed on every path, and after a failure the communicators are
+// aborted and the context refuses further frames.
+template <class Call>
+int rccl_group(ptg_multi *m, const char *what, Call &&call)
+{
+    const int n = (int)m->shards.size();
+    for (int k = n - 1; k >= 0; --k)
+        MULTI_HIP(hipSetDevice(m->shards[k].id));
+    ncclResult_t r = ncclGroupStart();
+    if (r != ncclSuccess)
+        return nccl_fail("ncclGroupStart", r);
+    int rc = PTG_OK;
+    for (int k = 0; k < n && rc == PTG_OK; ++k) {
+        Shard &s = m->shards[k];
+        (void)hipSetDevice(s.id);
+        r = call(k, s);
+        if (r != ncclSuccess)
+            rc = nccl_fail(what, r);
+    }
+    // the group is closed on every path (an error inside it must not leave
+    // this thread's RCCL group open) ...
+    const ncclResult_t re = ncclGroupEnd();
+    if (rc != PTG_OK || re != ncclSuccess) {
+        // ... but a partial group must not run without its peers: the
+        // queued collectives are aborted with the communicators, and the
+        // context refuses further frames
+        m->broken = true;
+        for (Shard &s : m->shards)
+            if (s.comm) {
+                (void)hipSetDevice(s.id);
+                (void)ncclCommAbort(s.comm);
+                s.comm = nullptr;
+            }
+        return rc != PTG_OK ? rc : nccl_fail("ncclGroupEnd", re);
+    }
+    return PTG_OK;
+}
+
 // ONE gather of the equal-size slabs to the root (RCCL: one ncclGather per
 // rank inside a group, rank-major on the root -- rccl.h:745; local shards: the
 // same layout by device copies after each shard's slab is complete) and the
@@ -316,39 +388,13 @@ int gather_unshard_device(ptg_multi *m, const ptg_params *p, size_t slab_elems)
     const int n = (int)m->shards.size();
     Shard &root = m->shards[0];
     if (m->rccl) {
-        // every device is made current once BEFORE the group opens, so that
-        // inside it only the ncclGather calls can fail
-        for (int k = n - 1; k >= 0; --k)
-            MULTI_HIP(hipSetDevice(m->shards[k].id));
-        ncclResult_t r = ncclGroupStart();
-        if (r != ncclSuccess)
-            return nccl_fail("ncclGroupStart", r);
-        int rc = PTG_OK;
-        for (int k = 0; k < n && rc == PTG_OK; ++k) {
-            Shard &s = m->shards[k];
-            (void)hipSetDevice(s.id);
-            r = k == m->inject_gather_fault
-                    ? ncclInvalidArgument
-                    : ncclGather(s.slab, k == 0 ? m->gathered : nullptr, slab_elems, ncclFloat, 0, s.comm, s.stream);
-            if (r != ncclSuccess)
-                rc = nccl_fail("ncclGather", r);
-        }
-        // the group is closed on every path (an error inside it must not leave
-        // this thread's RCCL group open) ...
-        const ncclResult_t re = ncclGroupEnd();
-        if (rc != PTG_OK || re != ncclSuccess) {
-            // ... but a partial group must not run without its peers: the
-            // queued collectives are aborted with the communicators, and the
-            // context refuses further frames
-            m->broken = true;
-            for (Shard &s : m->shards)
-                if (s.comm) {
-                    (void)hipSetDevice(s.id);
-                    (void)ncclCommAbort(s.comm);
-                    s.comm = nullptr;
-                }
-            return rc != PTG_OK ? rc : nccl_fail("ncclGroupEnd", re);
-        }
+        const int rc = rccl_group(m, "ncclGather", [&](int k, Shard &s) {
+            return k == m->inject_gather_fault
+                       ? ncclInvalidArgument
+                       : ncclGather(s.slab, k == 0 ? m->gathered : nullptr, slab_elems, ncclFloat, 0, s.comm, s.stream);
+        });
+        if (rc)
+            return rc;
         MULTI_HIP(hipSetDevice(root.id));
     } else {
         MULTI_HIP(hipSetDevice(root.id));
@@ -385,6 +431,272 @@ int gather_unshard(ptg_multi *m, const ptg_params *p, size_t slab_elems)
     MULTI_HIP(hipMemcpyAsync(m->host.data(), m->image, image_elems * sizeof(float), hipMemcpyDeviceToHost,
                              root.stream));
     return sync_all(m);
+}
+
+// ---- noise-target and adaptive frames (include/ptgpu.h "several GPUs") ----
+// The contexts' statistics are integers that add across shards ([2]: max), the
+// sums are exact and the RNG is keyed by the global pixel: what is left to the
+// host is to hand every shard the whole frame's over bytes and to decide for
+// the frame.
+
+int check_noise_args(double rel_error, double floor, const char *who)
+{
+    if (!(floor > 0.0) || !(rel_error >= 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": floor must be > 0 and rel_error >= 0");
+    return PTG_OK;
+}
+
+// the per-shard byte slabs, statistics and count slab for a frame of this
+// size (grown, never shrunk), the pinned statistics of all shards
+int reserve_adaptive(ptg_multi *m, const ptg_params *p, size_t &slab_pixels)
+{
+    const int n = (int)m->shards.size();
+    int32_t rows = 0;
+    int rc = ptg_shard_rows(p->height, p->band_rows, n, &rows);
+    if (rc)
+        return rc;
+    slab_pixels = (size_t)rows * p->width;
+    for (Shard &s : m->shards) {
+        if (s.ad_pixels >= slab_pixels)
+            continue;
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipStreamSynchronize(s.stream));
+        for (void **q : {(void **)&s.over, (void **)&s.over_all, (void **)&s.stats, (void **)&s.cnt}) {
+            if (*q)
+                MULTI_HIP(hipFree(*q));
+            *q = nullptr;
+        }
+        s.ad_pixels = 0;
+        if (hipMalloc(&s.over, slab_pixels) != hipSuccess || hipMalloc(&s.over_all, (size_t)n * slab_pixels) != hipSuccess ||
+            hipMalloc(&s.stats, kStats * sizeof(unsigned long long)) != hipSuccess ||
+            hipMalloc(&s.cnt, slab_pixels * sizeof(int32_t)) != hipSuccess)
+            return fail(PTG_ERR_OUT_OF_MEMORY, "multi: hipMalloc of the adaptive-sampling slabs failed");
+        MULTI_HIP(hipMemsetAsync(s.stats, 0, kStats * sizeof(unsigned long long), s.stream));
+        s.ad_pixels = slab_pixels;
+    }
+    if (!m->host_stats &&
+        hipHostMalloc(reinterpret_cast<void **>(&m->host_stats), (size_t)n * kStats * sizeof(unsigned long long)) != hipSuccess)
+        return fail(PTG_ERR_OUT_OF_MEMORY, "multi: hipHostMalloc of the statistics failed");
+    return PTG_OK;
+}
+
+// the first `count` statistics of every shard to the host: n asynchronous
+// copies, then the pass's one synchronisation; the shards' values combined
+// into out ([2]: max, the others add)
+int read_stats(ptg_multi *m, int count, unsigned long long *out)
+{
+    const int n = (int)m->shards.size();
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipMemcpyAsync(m->host_stats + (size_t)k * kStats, s.stats, count * sizeof(unsigned long long),
+                                 hipMemcpyDeviceToHost, s.stream));
+    }
+    int rc = sync_all(m);
+    if (rc)
+        return rc;
+    for (int i = 0; i < count; ++i)
+        out[i] = 0;
+    for (int k = 0; k < n; ++k)
+        for (int i = 0; i < count; ++i) {
+            const unsigned long long v = m->host_stats[(size_t)k * kStats + i];
+            out[i] = i == 2 ? (out[i] > v ? out[i] : v) : out[i] + v;
+        }
+    return PTG_OK;
+}
+
+int multi_noise(ptg_multi *m, const ptg_params *p, int32_t samples_done, double rel_error, double floor,
+                unsigned long long *stats)
+{
+    size_t slab_pixels = 0;
+    int rc = reserve_adaptive(m, p, slab_pixels);
+    if (rc)
+        return rc;
+    const int n = (int)m->shards.size();
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipMemsetAsync(s.stats, 0, 4 * sizeof(unsigned long long), s.stream));
+        const ptg_params q = shard_params(p, k, n);
+        if ((rc = ptg_noise_device(s.ctx, &q, samples_done, rel_error, floor, nullptr, nullptr, s.stats, s.stream)))
+            return rc;
+    }
+    return read_stats(m, 4, stats);
+}
+
+// ONE all-gather of the shards' over bytes onto every device, rank-major
+// (RCCL: one ncclAllGather per rank inside a group; local shards: the same
+// layout by device copies after each shard's slab is complete)
+int all_gather_over(ptg_multi *m, size_t slab_pixels)
+{
+    const int n = (int)m->shards.size();
+    if (m->rccl)
+        return rccl_group(m, "ncclAllGather", [&](int, Shard &s) {
+            return ncclAllGather(s.over, s.over_all, slab_pixels, ncclUint8, s.comm, s.stream);
+        });
+    for (Shard &s : m->shards) {
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipEventRecord(s.done, s.stream));
+    }
+    for (int j = 0; j < n; ++j) {
+        Shard &d = m->shards[j];
+        MULTI_HIP(hipSetDevice(d.id));
+        for (int k = 0; k < n; ++k) {
+            Shard &s = m->shards[k];
+            if (k != j)
+                MULTI_HIP(hipStreamWaitEvent(d.stream, s.done, 0));
+            MULTI_HIP(hipMemcpyAsync(d.over_all + (size_t)k * slab_pixels, s.over, slab_pixels, hipMemcpyDeviceToDevice,
+                                     d.stream));
+        }
+    }
+    return PTG_OK;
+}
+
+int multi_select(ptg_multi *m, const ptg_params *p, double rel_error, double floor, int32_t dilate,
+                 unsigned long long *stats)
+{
+    size_t slab_pixels = 0;
+    int rc = reserve_adaptive(m, p, slab_pixels);
+    if (rc)
+        return rc;
+    const int n = (int)m->shards.size();
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipMemsetAsync(s.stats, 0, 6 * sizeof(unsigned long long), s.stream));
+        const ptg_params q = shard_params(p, k, n);
+        if ((rc = ptg_select_over_device(s.ctx, &q, rel_error, floor, s.over, nullptr, s.stats, s.stream)))
+            return rc;
+    }
+    if ((rc = all_gather_over(m, slab_pixels)))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        const ptg_params q = shard_params(p, k, n);
+        if ((rc = ptg_set_active_gathered_device(s.ctx, &q, s.over_all, dilate, s.stats, s.stream)))
+            return rc;
+    }
+    unsigned long long st[6];
+    if ((rc = read_stats(m, 6, st)))
+        return rc;
+    for (int k = 0; k < n; ++k) {
+        // the shard's own unit count sizes its next pass (a shard without an
+        // active unit: the smallest launch, not the host-side bound)
+        const long long u = (long long)m->host_stats[(size_t)k * kStats + 5];
+        m->shards[k].max_units = u > 0 ? u : 1;
+    }
+    if (stats)
+        std::copy(st, st + 6, stats);
+    return PTG_OK;
+}
+
+int multi_set_mask(ptg_multi *m, const ptg_params *p, const uint8_t *mask)
+{
+    size_t slab_pixels = 0;
+    int rc = reserve_adaptive(m, p, slab_pixels);
+    if (rc)
+        return rc;
+    const int n = (int)m->shards.size();
+    const int W = p->width, H = p->height, br = p->band_rows;
+    if (mask) {
+        m->host_mask.assign((size_t)n * slab_pixels, 0);
+        for (int r = 0; r < H; ++r) {
+            const int band = r / br;
+            const size_t slab_row = (size_t)(band / n) * br + (size_t)(r - band * br);
+            std::memcpy(m->host_mask.data() + (size_t)(band % n) * slab_pixels + slab_row * W, mask + (size_t)r * W, W);
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        const ptg_params q = shard_params(p, k, n);
+        if (mask) {
+            MULTI_HIP(hipSetDevice(s.id));
+            MULTI_HIP(hipMemcpyAsync(s.over, m->host_mask.data() + (size_t)k * slab_pixels, slab_pixels,
+                                     hipMemcpyHostToDevice, s.stream));
+        }
+        if ((rc = ptg_set_active_mask_device(s.ctx, &q, mask ? s.over : nullptr, nullptr, s.stream)))
+            return rc;
+        s.max_units = 0;  // the host-side bound
+    }
+    return mask ? sync_all(m) : PTG_OK;  // (the staging buffers may be reused)
+}
+
+int multi_accumulate_active(ptg_multi *m, const ptg_params *p, int32_t add_samples, bool count)
+{
+    const int n = (int)m->shards.size();
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        const ptg_params q = shard_params(p, k, n);
+        const int rc = ptg_accumulate_active_device(s.ctx, &q, add_samples, s.max_units, count ? s.stats + 6 : nullptr,
+                                                    s.stream);
+        if (rc)
+            return rc;
+    }
+    return PTG_OK;
+}
+
+int multi_resolve_active(ptg_multi *m, const ptg_params *p)  // into m->host
+{
+    size_t slab_elems = 0;
+    int rc = reserve(m, p, slab_elems);
+    if (rc)
+        return rc;
+    const int n = (int)m->shards.size();
+    for (int k = 0; k < n; ++k) {
+        const ptg_params q = shard_params(p, k, n);
+        if ((rc = ptg_resolve_active_device(m->shards[k].ctx, &q, m->shards[k].slab, m->shards[k].stream)))
+            return rc;
+    }
+    return gather_unshard(m, p, slab_elems);
+}
+
+int multi_read_counts(ptg_multi *m, const ptg_params *p, int32_t *counts)
+{
+    size_t slab_pixels = 0;
+    int rc = reserve_adaptive(m, p, slab_pixels);
+    if (rc)
+        return rc;
+    const int n = (int)m->shards.size();
+    m->host_cnt.resize((size_t)n * slab_pixels);
+    for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
+        const ptg_params q = shard_params(p, k, n);
+        if ((rc = ptg_read_sample_counts_device(s.ctx, &q, s.cnt, s.stream)))
+            return rc;
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipMemcpyAsync(m->host_cnt.data() + (size_t)k * slab_pixels, s.cnt, slab_pixels * sizeof(int32_t),
+                                 hipMemcpyDeviceToHost, s.stream));
+    }
+    if ((rc = sync_all(m)))
+        return rc;
+    const int W = p->width, br = p->band_rows;
+    for (int r = 0; r < p->height; ++r) {  // the un-shard, on the host
+        const int band = r / br;
+        const size_t slab_row = (size_t)(band / n) * br + (size_t)(r - band * br);
+        std::memcpy(counts + (size_t)r * W, m->host_cnt.data() + (size_t)(band % n) * slab_pixels + slab_row * W,
+                    (size_t)W * sizeof(int32_t));
+    }
+    return PTG_OK;
+}
+
+double rho_of_bits(unsigned long long bits)
+{
+    const uint32_t b = (uint32_t)bits;
+    float rho;
+    std::memcpy(&rho, &b, sizeof(rho));
+    return (double)rho;
+}
+
+// the drivers' argument checks after the frame's (before any device work); the pass ends
+int check_driver(const ptg_params *p, double rel_error, double floor, double max_fraction, int32_t min_samples,
+                 const char *who, int32_t *ends, int32_t *n_ends)
+{
+    int rc = check_noise_args(rel_error, floor, who);
+    if (rc)
+        return rc;
+    if (!(max_fraction >= 0.0 && max_fraction < 1.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": max_fraction must be in [0, 1)");
+    return ptg_noise_schedule(min_samples, p->samples, ends, PTG_NOISE_MAX_PASSES, n_ends);
 }
 
 }  // namespace
@@ -493,6 +805,217 @@ int ptg_multi_resolve(ptg_multi *m, const ptg_params *params, int32_t samples_do
         return rc;
     const size_t image_elems = (size_t)params->width * params->height * 3;
     std::copy(m->host.begin(), m->host.begin() + image_elems, image_rgb);
+    return PTG_OK;
+}
+
+int ptg_multi_noise(ptg_multi *m, const ptg_params *params, int32_t samples_done, double rel_error, double floor,
+                    unsigned long long *stats)
+{
+    int rc = check_frame(m, params);
+    if (rc)
+        return rc;
+    if (!stats)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_noise: stats is NULL");
+    if (samples_done < 2 || samples_done > params->samples)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_noise: samples_done must be in [2, samples]");
+    if ((rc = check_noise_args(rel_error, floor, "multi_noise")))
+        return rc;
+    m->timed = false;  // the image / events no longer describe a frame_device frame
+    DeviceGuard g;
+    return multi_noise(m, params, samples_done, rel_error, floor, stats);
+}
+
+int ptg_multi_set_active_mask(ptg_multi *m, const ptg_params *params, const uint8_t *mask)
+{
+    int rc = check_frame(m, params);
+    if (rc)
+        return rc;
+    m->timed = false;
+    DeviceGuard g;
+    return multi_set_mask(m, params, mask);
+}
+
+int ptg_multi_select_active(ptg_multi *m, const ptg_params *params, double rel_error, double floor, int32_t dilate,
+                            unsigned long long *stats)
+{
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_noise_args(rel_error, floor, "multi_select_active")))
+        return rc;
+    if (dilate < 0 || dilate > 8)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_select_active: dilate must be in [0, 8]");
+    m->timed = false;
+    DeviceGuard g;
+    return multi_select(m, params, rel_error, floor, dilate, stats);
+}
+
+int ptg_multi_accumulate_active(ptg_multi *m, const ptg_params *params, int32_t add_samples)
+{
+    int rc = check_frame(m, params);
+    if (rc)
+        return rc;
+    if (add_samples < 0)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_accumulate_active: add_samples must be >= 0");
+    m->timed = false;
+    DeviceGuard g;
+    return multi_accumulate_active(m, params, add_samples, /*count=*/false);
+}
+
+int ptg_multi_resolve_active(ptg_multi *m, const ptg_params *params, float *image_rgb)
+{
+    int rc = check_frame(m, params);
+    if (rc)
+        return rc;
+    if (!image_rgb)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_resolve_active: image is NULL");
+    m->timed = false;
+    DeviceGuard g;
+    if ((rc = multi_resolve_active(m, params)))
+        return rc;
+    const size_t image_elems = (size_t)params->width * params->height * 3;
+    std::copy(m->host.begin(), m->host.begin() + image_elems, image_rgb);
+    return PTG_OK;
+}
+
+int ptg_multi_read_sample_counts(ptg_multi *m, const ptg_params *params, int32_t *counts)
+{
+    int rc = check_frame(m, params);
+    if (rc)
+        return rc;
+    if (!counts)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_read_sample_counts: counts is NULL");
+    m->timed = false;
+    DeviceGuard g;
+    return multi_read_counts(m, params, counts);
+}
+
+int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
+                              double *image_rgb, ptg_noise_report *report)
+{
+    if (!image_rgb || !target)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_to_noise: NULL image or target");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
+                                 "multi_render_to_noise", ends, &n_ends)))
+        return rc;
+    m->timed = false;
+    DeviceGuard g;
+    ptg_noise_report rep{};
+    ptg_params p = *params;
+    p.flags |= PTG_FLAG_MOMENTS;
+    if ((rc = ptg_multi_reset_accumulation(m, &p)))
+        return rc;
+    int32_t done = 0;
+    for (int k = 0; k < n_ends; ++k) {
+        unsigned long long st[4];
+        if ((rc = ptg_multi_accumulate(m, &p, done, ends[k])))
+            return rc;
+        done = ends[k];
+        if ((rc = multi_noise(m, &p, done, target->rel_error, target->floor, st)))
+            return rc;
+        rep.samples_done = done;
+        rep.passes = k + 1;
+        rep.pixels = st[3];
+        rep.pixels_over = st[0];
+        rep.pass_samples[k] = done;
+        rep.pass_over[k] = st[0];
+        rep.max_rho = rho_of_bits(st[2]);
+        rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
+        rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
+        if (rep.converged)
+            break;
+    }
+    size_t slab_elems = 0;
+    if ((rc = reserve(m, &p, slab_elems)))
+        return rc;
+    const int n = (int)m->shards.size();
+    for (int k = 0; k < n; ++k) {
+        const ptg_params q = shard_params(&p, k, n);
+        if ((rc = ptg_resolve_device(m->shards[k].ctx, &q, done, m->shards[k].slab, m->shards[k].stream)))
+            return rc;
+    }
+    if ((rc = gather_unshard(m, &p, slab_elems)))
+        return rc;
+    const size_t image_elems = (size_t)p.width * p.height * 3;
+    for (size_t i = 0; i < image_elems; ++i)
+        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
+    if (report)
+        *report = rep;
+    return PTG_OK;
+}
+
+int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
+                              double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report)
+{
+    if (!image_rgb || !target)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_adaptive: NULL image or target");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
+                                 "multi_render_adaptive", ends, &n_ends)))
+        return rc;
+    if (target->dilate < 0 || target->dilate > 8)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_adaptive: dilate must be in [0, 8]");
+    m->timed = false;
+    DeviceGuard g;
+    ptg_adaptive_report rep{};
+    const ptg_params &p = *params;
+    const bool count = (p.flags & (PTG_FLAG_COUNT_TESTS | PTG_FLAG_COUNT_NONFINITE)) != 0;
+    size_t slab_pixels = 0;
+    if ((rc = reserve_adaptive(m, &p, slab_pixels)))
+        return rc;
+    for (Shard &s : m->shards) {  // the kernel counters of the frame
+        MULTI_HIP(hipSetDevice(s.id));
+        MULTI_HIP(hipMemsetAsync(s.stats + 6, 0, 4 * sizeof(unsigned long long), s.stream));
+    }
+    if ((rc = ptg_multi_reset_accumulation(m, &p)) || (rc = multi_set_mask(m, &p, nullptr)))  // pass 0: every pixel
+        return rc;
+    unsigned long long active = (unsigned long long)p.width * p.height;
+    int32_t done = 0;
+    for (int k = 0; k < n_ends; ++k) {
+        unsigned long long st[6];
+        const int32_t add = ends[k] - done;
+        if ((rc = multi_accumulate_active(m, &p, add, count)))
+            return rc;
+        done = ends[k];
+        rep.total_samples += active * (unsigned long long)add;
+        if ((rc = multi_select(m, &p, target->rel_error, target->floor, target->dilate, st)))
+            return rc;
+        rep.passes = k + 1;
+        rep.max_samples = done;
+        rep.pixels = st[3];
+        rep.pixels_over = st[0];
+        rep.pass_added[k] = add;
+        rep.pass_over[k] = st[0];
+        rep.pass_active[k] = st[4];
+        rep.max_rho = rho_of_bits(st[2]);
+        rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
+        rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
+        if (rep.converged)
+            break;
+        active = st[4];
+    }
+    if ((rc = multi_resolve_active(m, &p)) || (sample_counts && (rc = multi_read_counts(m, &p, sample_counts))))
+        return rc;
+    if (count) {
+        const int n = (int)m->shards.size();
+        for (int k = 0; k < n; ++k) {  // into the pinned statistics, one wait for all
+            Shard &s = m->shards[k];
+            MULTI_HIP(hipSetDevice(s.id));
+            MULTI_HIP(hipMemcpyAsync(m->host_stats + (size_t)k * kStats + 6, s.stats + 6, 4 * sizeof(unsigned long long),
+                                     hipMemcpyDeviceToHost, s.stream));
+        }
+        if ((rc = sync_all(m)))
+            return rc;
+        for (int k = 0; k < n; ++k)
+            for (int i = 0; i < 4; ++i)
+                rep.counters[i] += m->host_stats[(size_t)k * kStats + 6 + i];
+    }
+    const size_t image_elems = (size_t)p.width * p.height * 3;
+    for (size_t i = 0; i < image_elems; ++i)
+        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
+    if (report)
+        *report = rep;
     return PTG_OK;
 }
 
@@ -638,15 +1161,54 @@ int ptg_render_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_came
 {
     if (!params || !image_rgb || !devices || n_devices < 1)
         return fail(PTG_ERR_INVALID_ARGUMENT, "render_multi: NULL argument or no device");
-    ptg_multi probe;  // argument checks before any device work
-    probe.shards.resize(1);
-    int rc = check_frame(&probe, params);
+    int rc = check_frame_params(params);  // argument checks before any device work
     if (rc)
         return rc;
     ptg_multi *m = nullptr;
     if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
         return rc;
     rc = ptg_multi_render(m, params, image_rgb);
+    ptg_multi_destroy(m);
+    return rc;
+}
+
+int ptg_render_to_noise_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                              const ptg_params *params, const int *devices, int n_devices,
+                              const ptg_noise_target *target, double *image_rgb, ptg_noise_report *report)
+{
+    if (!params || !image_rgb || !target || !devices || n_devices < 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise_multi: NULL argument or no device");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    int rc = check_frame_params(params);  // argument checks before any device work
+    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
+                                 "render_to_noise_multi", ends, &n_ends)))
+        return rc;
+    ptg_multi *m = nullptr;
+    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
+        return rc;
+    rc = ptg_multi_render_to_noise(m, params, target, image_rgb, report);
+    ptg_multi_destroy(m);
+    return rc;
+}
+
+int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                              const ptg_params *params, const int *devices, int n_devices,
+                              const ptg_adaptive_target *target, double *image_rgb, int32_t *sample_counts,
+                              ptg_adaptive_report *report)
+{
+    if (!params || !image_rgb || !target || !devices || n_devices < 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_multi: NULL argument or no device");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    int rc = check_frame_params(params);  // argument checks before any device work
+    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
+                                 "render_adaptive_multi", ends, &n_ends)))
+        return rc;
+    if (target->dilate < 0 || target->dilate > 8)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_multi: dilate must be in [0, 8]");
+    ptg_multi *m = nullptr;
+    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
+        return rc;
+    rc = ptg_multi_render_adaptive(m, params, target, image_rgb, sample_counts, report);
     ptg_multi_destroy(m);
     return rc;
 }

@@ -2251,6 +2251,106 @@ __global__ __launch_bounds__(256) void list_rows_kernel(KArgs A, const uint8_t *
         row_count[row] = base;
 }
 
+// Step 1 for a shard of a multi-device frame (ptg_set_active_gathered_device):
+// list_rows_kernel's output from the over bytes of the WHOLE frame, gathered
+// rank-major (shard_count slabs of slab_rows * W bytes, ptg_unshard_device's
+// layout) -- with interleaved bands the window rows of a pixel live in other
+// shards' slabs.  Separable, per tile of 256 columns:
+//   1. the row's <= 17 window rows (clipped to the image) are mapped to
+//      gathered slab rows once, in LDS (workgroup-uniform);
+//   2. each lane ORs its column over those rows (coalesced byte loads); the
+//      wave's ballot is a 64-bit word in LDS -- 4 words a tile, and a fifth
+//      from the first `dilate` columns right of it (the seam: x = 255 needs
+//      columns up to 263); the word left of the tile is carried in a register;
+//   3. every wave dilates the 4 words horizontally, each OR-ed with its two
+//      neighbours shifted by -dilate..+dilate (dilate <= 8 < 64) -- scalar
+//      work; its own word gives the lanes' flags, the popcounts of all four
+//      the ranks (no second pass through LDS).
+// Columns >= W and rows outside the image contribute no set bit, so the window
+// is clipped; slab rows past the image are never read.
+constexpr int kMaxDilate = 8;
+
+__device__ __forceinline__ unsigned long long dilate_word(unsigned long long l, unsigned long long c,
+                                                          unsigned long long r, int dilate)
+{
+    unsigned long long d = c;
+    for (int k = 1; k <= dilate; ++k)  // column b -+ k set: pixel b is active
+        d |= (c << k) | (l >> (64 - k)) | (c >> k) | (r << (64 - k));
+    return d;
+}
+
+__global__ __launch_bounds__(256) void list_rows_gathered_kernel(KArgs A, const uint8_t *__restrict__ gathered,
+                                                                 int dilate, int *__restrict__ list,
+                                                                 int *__restrict__ row_count)
+{
+    const int row = blockIdx.x;
+    const int r = out_row_of(A, row);
+    if (r >= A.H) {  // a slab row past the image (the whole workgroup)
+        if (threadIdx.x == 0)
+            row_count[row] = 0;
+        return;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ long long win_row[2 * kMaxDilate + 1];  // gathered slab row (rank-major) of each window row
+    __shared__ unsigned long long word[5];             // column-OR ballots: the tile's four, the right seam's
+    const int r0 = r - dilate > 0 ? r - dilate : 0;
+    const int r1 = r + dilate < A.H - 1 ? r + dilate : A.H - 1;
+    const int n_win = r1 - r0 + 1;
+    if ((int)threadIdx.x < n_win) {
+        const int rr = r0 + (int)threadIdx.x;
+        const int band = rr / A.band_rows;
+        const int rank = band % A.shard_count;
+        win_row[threadIdx.x] = (long long)rank * A.slab_rows + (long long)(band / A.shard_count) * A.band_rows +
+                               (rr - band * A.band_rows);
+    }
+    __syncthreads();
+    auto column_or = [&](int x, bool on) -> unsigned long long {
+        unsigned v = 0u;
+        if (on && x < A.W)
+            for (int j = 0; j < n_win; ++j)
+                v |= gathered[(size_t)win_row[j] * A.W + x];
+        return __ballot(v != 0u);
+    };
+    unsigned long long left = 0ull;  // the word of the 64 columns left of the tile (workgroup-uniform)
+    int base = 0;                    // the row's active pixels left of this tile (workgroup-uniform)
+    for (int x0 = 0; x0 < A.W; x0 += 256) {
+        const int x = x0 + (int)threadIdx.x;
+        const unsigned long long own = column_or(x, true);
+        if (lane == 0)
+            word[wv] = own;
+        if (wv == 0) {  // the seam: the first `dilate` columns of the next tile
+            const unsigned long long seam = column_or(x + 256, lane < dilate);
+            if (lane == 0)
+                word[4] = seam;
+        }
+        __syncthreads();
+        unsigned long long w[6];
+        w[0] = left;
+        for (int i = 0; i < 5; ++i)
+            w[i + 1] = word[i];
+        int before = 0, tile = 0;
+        unsigned long long mine = 0ull;
+        for (int i = 0; i < 4; ++i) {
+            const int nv = A.W - (x0 + 64 * i);  // the word's columns inside the image
+            const unsigned long long valid = nv >= 64 ? ~0ull : (nv > 0 ? (1ull << nv) - 1ull : 0ull);
+            const unsigned long long d = dilate_word(w[i], w[i + 1], w[i + 2], dilate) & valid;
+            const int c = (int)__popcll(d);
+            before += i < wv ? c : 0;
+            tile += c;
+            mine = i == wv ? d : mine;
+        }
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mine >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((unsigned)mine, 0u));
+        if ((mine >> lane) & 1ull)
+            list[(size_t)row * A.W + base + before + rank] = x;  // base + before + rank < the row's count <= W
+        base += tile;
+        left = w[4];
+        __syncthreads();  // word is rewritten by the next tile
+    }
+    if (threadIdx.x == 0)
+        row_count[row] = base;
+}
+
 // Step 2, one workgroup: a row's pixels are cut into units of pixels_per_wave
 // (units never span rows); row_unit0[row] = the units of the rows before it
 // (an exclusive scan: shuffles within a wave, LDS across the workgroup, a
@@ -2925,12 +3025,16 @@ int begin_adaptive(ptg_context *ctx, const ptg_params *p, KArgs &A, hipStream_t 
     return ensure_adaptive(ctx, A, s);
 }
 
-// List-building steps 2 and 3 after step 1 (list_rows_kernel on `flags`)
+// List-building steps 2 and 3 after step 1: list_rows_kernel on `flags`, or,
+// gathered, list_rows_gathered_kernel on the whole frame's rank-major slabs
 int build_list(ptg_context *ctx, const ptg_params *p, const KArgs &A, const uint8_t *flags, int dilate,
-               unsigned long long *d_info, unsigned long long *d_stats, hipStream_t s)
+               unsigned long long *d_info, unsigned long long *d_stats, hipStream_t s, bool gathered = false)
 {
     if (A.slab_rows > 0) {
-        list_rows_kernel<<<A.slab_rows, 256, 0, s>>>(A, flags, dilate, ctx->d_list, ctx->d_row_count);
+        if (gathered)
+            list_rows_gathered_kernel<<<A.slab_rows, 256, 0, s>>>(A, flags, dilate, ctx->d_list, ctx->d_row_count);
+        else
+            list_rows_kernel<<<A.slab_rows, 256, 0, s>>>(A, flags, dilate, ctx->d_list, ctx->d_row_count);
         PTG_HIP(hipGetLastError());
     }
     list_units_kernel<<<1, 256, 0, s>>>(A.slab_rows, A.pixels_per_wave, ctx->d_row_count, ctx->d_row_unit0, ctx->d_rec,
@@ -3178,6 +3282,45 @@ int ptg_select_active_device(ptg_context *ctx, const ptg_params *params, double 
         A, ctx->d_acc2, ctx->d_counts, rel_error, floor, ctx->d_over, d_rho, d_stats);
     PTG_HIP(hipGetLastError());
     return build_list(ctx, params, A, ctx->d_over, dilate, nullptr, d_stats, s);
+}
+
+int ptg_select_over_device(ptg_context *ctx, const ptg_params *params, double rel_error, double floor,
+                           uint8_t *d_over, float *d_rho, unsigned long long *d_stats, void *stream)
+{
+    if (!ctx || !d_over)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "select_over: NULL context or output");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (!(floor > 0.0) || !(rel_error >= 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "select_over: floor must be > 0 and rel_error >= 0");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "select_over")))
+        return rc;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    const long long blocks = (pixels + 255) / 256;  // the kernel strides over the rest
+    select_over_kernel<<<(unsigned)(blocks < kNoiseBlocks ? blocks : kNoiseBlocks), 256, 0, s>>>(
+        A, ctx->d_acc2, ctx->d_counts, rel_error, floor, d_over, d_rho, d_stats);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_set_active_gathered_device(ptg_context *ctx, const ptg_params *params, const uint8_t *d_over_gathered,
+                                   int32_t dilate, unsigned long long *d_stats, void *stream)
+{
+    if (!ctx || !d_over_gathered)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "set_active_gathered: NULL context or over bytes");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (dilate < 0 || dilate > kMaxDilate)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "set_active_gathered: dilate must be in [0, 8]");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "set_active_gathered")))
+        return rc;
+    return build_list(ctx, params, A, d_over_gathered, dilate, nullptr, d_stats, s, /*gathered=*/true);
 }
 
 int ptg_accumulate_active_device(ptg_context *ctx, const ptg_params *params, int32_t add_samples, long long max_units,

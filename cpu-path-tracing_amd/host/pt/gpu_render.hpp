@@ -114,5 +114,58 @@ inline int render_image_adaptive(scene const &scn, camera const &cam, std::vecto
                                sample_counts ? sample_counts->data() : nullptr, &report);
 }
 
+// The two above on several GPUs of this process (ptg_render_to_noise_multi /
+// ptg_render_adaptive_multi): device k renders the interleaved rows
+// r = k mod N, the frame is decided as a whole; image, counts and report equal
+// the one-device overloads' bit for bit for any device list.
+inline int render_image_to_noise(scene const &scn, camera const &cam, std::vector<vec3> &image, int width, int height,
+                                 int samps, ptg_noise_target const &target, ptg_noise_report &report,
+                                 std::vector<int> const &devices, int num_subpixels = 2,
+                                 std::uint64_t seed = default_seed, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return ptg_render_to_noise_multi(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                                     reinterpret_cast<ptg_camera const *>(&cam), &p, devices.data(),
+                                     static_cast<int>(devices.size()), &target,
+                                     reinterpret_cast<double *>(image.data()), &report);
+}
+
+inline int render_image_adaptive(scene const &scn, camera const &cam, std::vector<vec3> &image, int width, int height,
+                                 int samps, ptg_adaptive_target const &target, ptg_adaptive_report &report,
+                                 std::vector<int> const &devices, std::vector<std::int32_t> *sample_counts = nullptr,
+                                 int num_subpixels = 2, std::uint64_t seed = default_seed, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    if (sample_counts)
+        sample_counts->assign(image.size(), 0);
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return ptg_render_adaptive_multi(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                                     reinterpret_cast<ptg_camera const *>(&cam), &p, devices.data(),
+                                     static_cast<int>(devices.size()), &target,
+                                     reinterpret_cast<double *>(image.data()),
+                                     sample_counts ? sample_counts->data() : nullptr, &report);
+}
+
 }  // namespace gpu
 }  // namespace pt

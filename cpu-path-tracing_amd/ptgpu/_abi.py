@@ -26,6 +26,10 @@ EXPORTS = (
     "ptg_noise_device", "ptg_read_moments_device", "ptg_noise_schedule", "ptg_render_to_noise",
     "ptg_set_active_mask_device", "ptg_select_active_device", "ptg_accumulate_active_device",
     "ptg_resolve_active_device", "ptg_read_sample_counts_device", "ptg_render_adaptive",
+    "ptg_select_over_device", "ptg_set_active_gathered_device",
+    "ptg_multi_noise", "ptg_multi_set_active_mask", "ptg_multi_select_active", "ptg_multi_accumulate_active",
+    "ptg_multi_resolve_active", "ptg_multi_read_sample_counts", "ptg_multi_render_to_noise",
+    "ptg_multi_render_adaptive", "ptg_render_to_noise_multi", "ptg_render_adaptive_multi",
 )
 
 
@@ -129,6 +133,22 @@ def lib():
             "ptg_read_sample_counts_device": (I, [P, C.POINTER(Params), P, P]),
             "ptg_render_adaptive": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(AdaptiveTarget), P, P,
                                         C.POINTER(AdaptiveReport)]),
+            "ptg_select_over_device": (I, [P, C.POINTER(Params), C.c_double, C.c_double, P, P, P, P]),
+            "ptg_set_active_gathered_device": (I, [P, C.POINTER(Params), P, C.c_int32, P, P]),
+            "ptg_multi_noise": (I, [P, C.POINTER(Params), C.c_int32, C.c_double, C.c_double, P]),
+            "ptg_multi_set_active_mask": (I, [P, C.POINTER(Params), P]),
+            "ptg_multi_select_active": (I, [P, C.POINTER(Params), C.c_double, C.c_double, C.c_int32, P]),
+            "ptg_multi_accumulate_active": (I, [P, C.POINTER(Params), C.c_int32]),
+            "ptg_multi_resolve_active": (I, [P, C.POINTER(Params), P]),
+            "ptg_multi_read_sample_counts": (I, [P, C.POINTER(Params), P]),
+            "ptg_multi_render_to_noise": (I, [P, C.POINTER(Params), C.POINTER(NoiseTarget), P,
+                                              C.POINTER(NoiseReport)]),
+            "ptg_multi_render_adaptive": (I, [P, C.POINTER(Params), C.POINTER(AdaptiveTarget), P, P,
+                                              C.POINTER(AdaptiveReport)]),
+            "ptg_render_to_noise_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I,
+                                              C.POINTER(NoiseTarget), P, C.POINTER(NoiseReport)]),
+            "ptg_render_adaptive_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I,
+                                              C.POINTER(AdaptiveTarget), P, P, C.POINTER(AdaptiveReport)]),
             "ptg_multi_inject_gather_fault_": (I, [P, I]),
             # internal (tests): n shards on one device, gathered by device copies
             "ptg_multi_create_local_": (I, [P, C.c_size_t, P, I, I, C.POINTER(C.c_void_p)]),

@@ -137,9 +137,23 @@ def render_to_noise(scn, cam, image: np.ndarray, width: int, height: int, sample
     check(lib().ptg_render_to_noise(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
                                     C.byref(p), int(device), C.byref(target), image.ctypes.data_as(C.c_void_p),
                                     C.byref(rep)), "ptg_render_to_noise")
+    return _noise_report(rep)
+
+
+def _noise_report(rep: NoiseReport) -> dict:
     return {"samples_done": rep.samples_done, "passes": rep.passes, "converged": rep.converged,
             "pixels": rep.pixels, "pixels_over": rep.pixels_over, "max_rho": rep.max_rho, "mean_rho": rep.mean_rho,
             "pass_samples": list(rep.pass_samples[:rep.passes]), "pass_over": list(rep.pass_over[:rep.passes])}
+
+
+def _adaptive_report(rep: AdaptiveReport) -> dict:
+    n = rep.passes
+    return {"passes": n, "converged": rep.converged, "max_samples": rep.max_samples, "pixels": rep.pixels,
+            "pixels_over": rep.pixels_over, "max_rho": rep.max_rho, "mean_rho": rep.mean_rho,
+            "total_samples": rep.total_samples,
+            "mean_samples": rep.total_samples / rep.pixels if rep.pixels else 0.0,
+            "counters": list(rep.counters), "pass_added": list(rep.pass_added[:n]),
+            "pass_over": list(rep.pass_over[:n]), "pass_active": list(rep.pass_active[:n])}
 
 
 def render_adaptive(scn, cam, image: np.ndarray, width: int, height: int, samples: int, rel_error: float,
@@ -167,13 +181,7 @@ def render_adaptive(scn, cam, image: np.ndarray, width: int, height: int, sample
                                     C.byref(p), int(device), C.byref(target), image.ctypes.data_as(C.c_void_p),
                                     counts.ctypes.data_as(C.c_void_p) if sample_counts else None, C.byref(rep)),
           "ptg_render_adaptive")
-    n = rep.passes
-    out = {"passes": n, "converged": rep.converged, "max_samples": rep.max_samples, "pixels": rep.pixels,
-           "pixels_over": rep.pixels_over, "max_rho": rep.max_rho, "mean_rho": rep.mean_rho,
-           "total_samples": rep.total_samples,
-           "mean_samples": rep.total_samples / rep.pixels if rep.pixels else 0.0,
-           "counters": list(rep.counters), "pass_added": list(rep.pass_added[:n]),
-           "pass_over": list(rep.pass_over[:n]), "pass_active": list(rep.pass_active[:n])}
+    out = _adaptive_report(rep)
     return (out, counts) if sample_counts else out
 
 
@@ -297,6 +305,78 @@ class MultiContext:
         check(lib().ptg_multi_resolve(self._h, C.byref(params), int(samples_done),
                                       self._image(image, params, np.float32)), "ptg_multi_resolve")
         return image
+
+    # ---- noise-target and adaptive frames over all devices (ptg_multi_noise ... ptg_multi_render_adaptive)
+    def noise(self, params: Params, samples_done: int, rel_error: float, floor: float) -> np.ndarray:
+        """Context.noise's four statistics (uint64 [4]) of the whole frame,
+        after accumulate() passes with FLAG_MOMENTS."""
+        st = np.zeros(4, dtype=np.uint64)
+        check(lib().ptg_multi_noise(self._h, C.byref(params), int(samples_done), float(rel_error), float(floor),
+                                    st.ctypes.data_as(C.c_void_p)), "ptg_multi_noise")
+        return st
+
+    def set_active_mask(self, params: Params, mask: Optional[np.ndarray] = None) -> None:
+        """The active list from a host byte mask ([H, W] uint8 in the image's
+        row order, != 0 is active; None: every pixel): each shard gets its rows."""
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, dtype=np.uint8)
+            if mask.size != params.width * params.height:
+                raise ValueError("mask must hold width*height bytes")
+        check(lib().ptg_multi_set_active_mask(self._h, C.byref(params),
+                                              mask.ctypes.data_as(C.c_void_p) if mask is not None else None),
+              "ptg_multi_set_active_mask")
+
+    def select_active(self, params: Params, rel_error: float, floor: float, dilate: int = 0) -> np.ndarray:
+        """Context.select_active for the whole frame (one all-gather of the
+        over bytes, so any dilate in 0..8): its six statistics (uint64 [6])."""
+        st = np.zeros(6, dtype=np.uint64)
+        check(lib().ptg_multi_select_active(self._h, C.byref(params), float(rel_error), float(floor), int(dilate),
+                                            st.ctypes.data_as(C.c_void_p)), "ptg_multi_select_active")
+        return st
+
+    def accumulate_active(self, params: Params, add_samples: int) -> None:
+        check(lib().ptg_multi_accumulate_active(self._h, C.byref(params), int(add_samples)),
+              "ptg_multi_accumulate_active")
+
+    def resolve_active(self, image: np.ndarray, params: Params) -> np.ndarray:
+        """Each pixel averaged over its own count, written to `image` (float32)."""
+        check(lib().ptg_multi_resolve_active(self._h, C.byref(params), self._image(image, params, np.float32)),
+              "ptg_multi_resolve_active")
+        return image
+
+    def read_sample_counts(self, params: Params) -> np.ndarray:
+        """The samples per sub-pixel of every pixel: int32 [H, W], the image's row order."""
+        counts = np.zeros((params.height, params.width), dtype=np.int32)
+        check(lib().ptg_multi_read_sample_counts(self._h, C.byref(params), counts.ctypes.data_as(C.c_void_p)),
+              "ptg_multi_read_sample_counts")
+        return counts
+
+    def render_to_noise(self, image: np.ndarray, params: Params, rel_error: float, floor: float = 0.01,
+                        max_fraction: float = 0.01, min_samples: int = 16) -> dict:
+        """render_to_noise() over all devices (added into `image`, float64):
+        the same image and report for any device count and band_rows."""
+        target = NoiseTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), 0)
+        rep = NoiseReport()
+        check(lib().ptg_multi_render_to_noise(self._h, C.byref(params), C.byref(target),
+                                              self._image(image, params, np.float64), C.byref(rep)),
+              "ptg_multi_render_to_noise")
+        return _noise_report(rep)
+
+    def render_adaptive(self, image: np.ndarray, params: Params, rel_error: float, floor: float = 0.01,
+                        max_fraction: float = 0.01, min_samples: int = 16, dilate: int = 1,
+                        sample_counts: bool = False):
+        """render_adaptive() over all devices (added into `image`, float64):
+        the same image, counts and report for any device count, band_rows and
+        dilate.  With sample_counts=True returns (report, counts [H, W] int32)."""
+        target = AdaptiveTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), int(dilate))
+        rep = AdaptiveReport()
+        counts = np.zeros((params.height, params.width), dtype=np.int32) if sample_counts else None
+        check(lib().ptg_multi_render_adaptive(self._h, C.byref(params), C.byref(target),
+                                              self._image(image, params, np.float64),
+                                              counts.ctypes.data_as(C.c_void_p) if sample_counts else None,
+                                              C.byref(rep)), "ptg_multi_render_adaptive")
+        out = _adaptive_report(rep)
+        return (out, counts) if sample_counts else out
 
 
 # every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel)
@@ -504,6 +584,38 @@ class Context:
         check(lib().ptg_select_active_device(self._h, C.byref(params), float(rel_error), float(floor), int(dilate),
                                              ptr(rho), ptr(stats), C.c_void_p(self._stream(stream))),
               "ptg_select_active_device")
+
+    def select_over(self, params: Params, rel_error: float, floor: float, over, rho=None, stats=None,
+                    stream=None) -> None:
+        """select_active's first step alone: this shard's over bytes to `over`
+        (uint8, slab rows*W: 1 where rho > rel_error), `rho` and `stats`
+        [0..3] (int64 [6]) as there; no list is built."""
+        import torch
+        self._check(over, torch.uint8, self._pixels(params))
+        if rho is not None:
+            self._check(rho, torch.float32, self._pixels(params))
+        if stats is not None:
+            self._check(stats, torch.int64, 6)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().ptg_select_over_device(self._h, C.byref(params), float(rel_error), float(floor), ptr(over),
+                                           ptr(rho), ptr(stats), C.c_void_p(self._stream(stream))),
+              "ptg_select_over_device")
+
+    def set_active_gathered(self, params: Params, over_gathered, dilate: int = 0, stats=None, stream=None) -> None:
+        """This shard's active list from the over bytes of the whole frame:
+        `over_gathered` (uint8) holds shard_count slabs of slab rows*W bytes,
+        rank-major (what an all-gather of select_over's slabs gives); active =
+        within `dilate` pixels of a set byte, across shard boundaries.  `stats`
+        (int64 [6], optional): [4] += active pixels, [5] += active units."""
+        import torch
+        self._check(over_gathered, torch.uint8, self._pixels(params) * params.shard_count)
+        if stats is not None:
+            self._check(stats, torch.int64, 6)
+        check(lib().ptg_set_active_gathered_device(self._h, C.byref(params), C.c_void_p(over_gathered.data_ptr()),
+                                                   int(dilate),
+                                                   C.c_void_p(stats.data_ptr()) if stats is not None else None,
+                                                   C.c_void_p(self._stream(stream))),
+              "ptg_set_active_gathered_device")
 
     def accumulate_active(self, params: Params, add_samples: int, max_units: int = 0, segments=None,
                           stream=None) -> None:

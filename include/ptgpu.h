@@ -388,6 +388,32 @@ int ptg_accumulate_active_device(ptg_context *ctx, const ptg_params *params, int
 int ptg_resolve_active_device(ptg_context *ctx, const ptg_params *params, float *d_slab, void *stream);
 int ptg_read_sample_counts_device(ptg_context *ctx, const ptg_params *params, int32_t *d_counts, void *stream);
 
+/* The selection in two steps, for a frame sharded over several contexts
+ * (ptg_multi_select_active; one rank per GPU would all-gather between them):
+ *
+ * ptg_select_over_device: step 1 of ptg_select_active_device on its own: the
+ * shard's over bytes to d_over (slab_rows * width bytes, 1 where rho >
+ * rel_error, 0 in slab rows past the image), rho to d_rho (optional),
+ * d_stats[0..3] (optional, 6 uint64 the caller zeroes; [4] and [5] are left to
+ * the second step).  No list is built.  Arguments and state rules as
+ * ptg_select_active_device's.
+ *
+ * ptg_set_active_gathered_device: this shard's active list from the over
+ * bytes of the WHOLE frame: d_over_gathered holds shard_count slabs of
+ * slab_rows * width bytes, rank-major, as all-gather lays them out
+ * (ptg_unshard_device's convention): the pixel (r, x) of the image lives in
+ * slab (r / band_rows) % shard_count, at slab row (r / band_rows /
+ * shard_count) * band_rows + r % band_rows.  A pixel of this shard is active
+ * when some byte of its (2 dilate + 1)^2 window, clipped to the image, is set
+ * -- the rows of the window are read from the slabs they live in, so any
+ * shard_count is accepted with dilate in [0, 8]; slab rows past the image are
+ * never read.  d_stats (optional): [4] += active pixels, [5] += active units.
+ * With shard_count 1 the list equals ptg_select_active_device's. */
+int ptg_select_over_device(ptg_context *ctx, const ptg_params *params, double rel_error, double floor,
+                           uint8_t *d_over, float *d_rho, unsigned long long *d_stats, void *stream);
+int ptg_set_active_gathered_device(ptg_context *ctx, const ptg_params *params, const uint8_t *d_over_gathered,
+                                   int32_t dilate, unsigned long long *d_stats, void *stream);
+
 typedef struct ptg_adaptive_target {
     double rel_error;    /* a pixel is over the target when rho > rel_error (>= 0) */
     double floor;        /* rho's denominator is max(pixel mean, floor) (> 0) */
@@ -423,6 +449,62 @@ typedef struct ptg_adaptive_report {
 int ptg_render_adaptive(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
                         const ptg_params *params, int device, const ptg_adaptive_target *target, double *image_rgb,
                         int32_t *sample_counts, ptg_adaptive_report *report);
+
+/* ---- noise-target and adaptive frames on several GPUs ------------------
+ * The entry points above on a ptg_multi (params->shard_count must be 1: the
+ * context shards the frame itself; PTG_FLAG_REFERENCE_F64 is
+ * PTG_ERR_UNSUPPORTED; the caller's current HIP device is restored on
+ * return).  Sums are exact, the statistics are integers that add across the
+ * shards ([2]: max) and the RNG is keyed by the global pixel, so for any
+ * device count, band_rows and dilate the image, the per-pixel sample counts,
+ * every report field and the kernel counters equal the one-device entry
+ * point's bit for bit.  The shards work concurrently on their own streams;
+ * each check synchronises with the host once, to read 48 bytes per shard.
+ * The contexts' state rules carry over: ptg_multi_accumulate /
+ * ptg_multi_resolve / ptg_multi_noise refuse while adaptive passes are in the
+ * sums, and the *_active entry points after a ptg_multi_accumulate pass,
+ * until ptg_multi_reset_accumulation.
+ *
+ * ptg_multi_noise: ptg_noise_device's four statistics (host, required) of
+ * the whole frame after ptg_multi_accumulate passes with PTG_FLAG_MOMENTS.
+ * ptg_multi_set_active_mask: the active list from a host byte mask of
+ * width * height bytes in the image's row order (NULL: every pixel); each
+ * shard receives its rows.  The region-of-interest entry point.
+ * ptg_multi_select_active: ptg_select_active_device for the frame: every
+ * shard's ptg_select_over_device, ONE all-gather of the over bytes onto every
+ * device (RCCL: one ncclAllGather per rank inside one group; a failure there
+ * aborts the communicators as the frame gather's does), every shard's
+ * ptg_set_active_gathered_device.  stats (host, optional): the six of
+ * ptg_select_active_device for the frame.  Each shard's own unit count sizes
+ * its next ptg_multi_accumulate_active pass.
+ * ptg_multi_accumulate_active: the next add_samples samples of every active
+ * pixel (asynchronous).  ptg_multi_resolve_active: each pixel averaged over
+ * its own count, W*H*3 floats written like ptg_multi_resolve.
+ * ptg_multi_read_sample_counts: width * height int32 in the image's row order. */
+int ptg_multi_noise(ptg_multi *m, const ptg_params *params, int32_t samples_done, double rel_error, double floor,
+                    unsigned long long *stats);
+int ptg_multi_set_active_mask(ptg_multi *m, const ptg_params *params, const uint8_t *mask);
+int ptg_multi_select_active(ptg_multi *m, const ptg_params *params, double rel_error, double floor, int32_t dilate,
+                            unsigned long long *stats);
+int ptg_multi_accumulate_active(ptg_multi *m, const ptg_params *params, int32_t add_samples);
+int ptg_multi_resolve_active(ptg_multi *m, const ptg_params *params, float *image_rgb);
+int ptg_multi_read_sample_counts(ptg_multi *m, const ptg_params *params, int32_t *counts);
+/* ptg_render_to_noise / ptg_render_adaptive on the context: the same
+ * schedule, stop rule and report, the frame decided as a whole; both ADD into
+ * image_rgb like the drop-in entry point.  ptg_render_to_noise_multi /
+ * ptg_render_adaptive_multi = ptg_multi_create + the call + ptg_multi_destroy
+ * on n_devices distinct GPUs, as ptg_render_multi. */
+int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
+                              double *image_rgb, ptg_noise_report *report);
+int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
+                              double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report);
+int ptg_render_to_noise_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                              const ptg_params *params, const int *devices, int n_devices,
+                              const ptg_noise_target *target, double *image_rgb, ptg_noise_report *report);
+int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                              const ptg_params *params, const int *devices, int n_devices,
+                              const ptg_adaptive_target *target, double *image_rgb, int32_t *sample_counts,
+                              ptg_adaptive_report *report);
 
 /* Reassemble shard_count gathered slabs (rank-major, as all-gather lays them
  * out) into the width*height*3 image. */
