@@ -1145,14 +1145,18 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
     // dielectric's Fresnel draw -- or, where it cannot refract, its
     // reflection's draw -- and the mirror's draw (main.cpp:46, :89, :62).
     // A dielectric lane reflected by its Fresnel draw takes the reflection's
-    // draw below (fres).  Each lane's draws keep their order and count;
-    // killed lanes advance a state their ended path no longer reads.
+    // draw as well: the block's shared second step below (fres_refl).
+    // Each lane's draws keep their order and count; killed lanes advance a
+    // state their ended path no longer reads.
     const uint32_t m1 = draw_bits(st);
-    [[maybe_unused]] bool fres = false;
+    bool fres_refl = false;  // dielectric lane reflected by its Fresnel draw (isG & fres & reflect)
     // its value u = m1 2^-24, converted once for the diffuse phi (fast
     // mode: v_sin / v_cos take revolutions) and the Fresnel compare
     const float u1 = (float)m1 * 0x1p-24f;
-    f3 nd = d;  // every lane sets it below (mirror lanes in the spec block)
+    // every lane sets it below (exact mode: reflecting lanes in the spec
+    // block; fast mode: the diffuse/dielectric block forms every material's
+    // direction, the spec block serves the waves that skip it)
+    f3 nd = d;
     // a wave with only mirror lanes skips the diffuse/dielectric work
     // (wave-uniform, exact: those lanes' values are all overwritten)
     // (the active lanes less the mirror lanes' mask, which the spec compare
@@ -1160,19 +1164,28 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
     // v_cndmask + v_cmp, one of mat != PTG_SPECULAR as another compare;
     // killed lanes of those materials run the block for nothing, their
     // values unused)
-    if ((__ballot(1) & ~__ballot(mat == PTG_SPECULAR)) != 0ull)
+    const bool dg_wave = (__ballot(1) & ~__ballot(mat == PTG_SPECULAR)) != 0ull;
+    if (dg_wave)
     {
         PTG_STAT(4);
 #if PTG_BLOCK_STATS == 3  // debug: wave cycles of the diffuse/dielectric block in [14]
         const unsigned long long dg_t0 = clock64();
 #endif
         {
+        // the second xorshift step, once for every lane of the block: the
+        // diffuse r and the draw of a reflection chosen by the Fresnel draw
+        // are the same step of the same state (st right after m1).  The
+        // lanes that take it -- diffuse, Fresnel-reflected -- adopt st2 in
+        // the one select after the Fresnel block; killed, mirror, totally
+        // reflected and refracting lanes keep st.
+        uint32_t st2 = st;
+        const uint32_t m2 = draw_bits(st2);
         // read only where isD (the ?: operands and the isD branch below):
         // no initial values to set for the other lanes
         float cp, sp, ra;
         if (isD) {  // main.cpp:46-47: phi = 2 pi u, r = u
             const uint32_t m_phi = m1;
-            ra = draw(st);
+            ra = (float)m2 * 0x1p-24f;  // draw()'s value of the shared step
             if constexpr (!kExact) {
                 cp = __builtin_amdgcn_cosf(u1);  // Math<false>::sincos2pi of m1
                 sp = __builtin_amdgcn_sinf(u1);
@@ -1181,9 +1194,13 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         }
         // op1: diffuse -> u = norm((|w.x| > 0.1 ? y : x) x w) (main.cpp:52); dielectric -> norm(d) (main.cpp:75)
         f3 uu = __builtin_fabsf(nn.x) > 0.1f ? mk3(nn.z, 0.0f, -nn.x) : mk3(0.0f, -nn.z, nn.y);
-        f3 v1 = isD ? uu : d;
-        const float r1 = Math<kExact>::rsqrt(dot3(v1, v1));
-        v1 = mk3(v1.x * r1, v1.y * r1, v1.z * r1);
+        const f3 v1raw = isD ? uu : d;
+        const float r1 = Math<kExact>::rsqrt(dot3(v1raw, v1raw));
+        // (fast mode: the normalising multiply waits for the Fresnel block --
+        // a reflecting lane keeps its d as it is; nothing before reads v1)
+        [[maybe_unused]] f3 v1 = v1raw;
+        if constexpr (kExact)
+            v1 = mk3(v1raw.x * r1, v1raw.y * r1, v1raw.z * r1);
         // (fast mode: only dielectric lanes read x0, and there v1 = d r1, so
         // v1.nn = (nn.d) r1 = kn r1 -- the dot the mirror already uses)
         const float x0 = kExact ? -dot3(v1, nn) : -(kn * r1);
@@ -1208,41 +1225,67 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
                 float x5 = (x2 * x2) * xm;
                 float R = __builtin_fmaf(1.0f - r0, x5, r0);
                 reflect = R > u1;
-                fres = true;
-                {  // the reflection's draw right after the Fresnel draw that chose it
-                    uint32_t st2 = st;
-                    (void)draw_bits(st2);
-                    st = reflect ? st2 : st;
-                }
+                fres_refl = reflect;  // (the reflection's draw after this one: st2, selected below)
             }
             spec = reflect;
         }
+        // one select for the shared second step (lane masks combined by the scalar unit)
+        st = (isD || fres_refl) ? st2 : st;
         // op3: diffuse -> cos theta = sqrt(1 - r); dielectric -> |r_out_parallel| (main.cpp:94)
-        const f3 perp = mk3(__builtin_fmaf(nn.x, cthG, v1.x) * ratio, __builtin_fmaf(nn.y, cthG, v1.y) * ratio,
-                            __builtin_fmaf(nn.z, cthG, v1.z) * ratio);
-        // (fast mode: nn and v1 are unit and v1.nn = -cos theta, so
-        // |perp|^2 = ratio^2 (1 - cos^2 theta) = rs2^2 -- one fma for the dot
-        // and its subtraction.  The one assumption added: cthG is the
-        // un-clamped x0 wherever the clamp does not bind, which is where s2^2
-        // is 1 - x0^2; then rs2^2 and |perp|^2 differ by roundings only.
-        // Where it binds, cthG = 1 and s2 = 0: the argument is 1, perp is
-        // within rounding of 0.)
-        float s3;  // both arguments >= 0
         if constexpr (!kExact) {
+            // One direction for every material of the block, as a linear
+            // combination of nn, vv = nn x v1 and v1:
+            //   diffuse     nn s3 + vv ss + v1 cs                (main.cpp:53-55)
+            //   reflection  d - 2 kn nn                          (main.cpp:60-67; v1 = d, not normalised)
+            //   refraction  r_out_perp - nn s3 with r_out_perp = (nn cthG + v1) ratio (main.cpp:93-96),
+            //               = nn (ratio cthG - s3) + v1 ratio
+            // in the operation order of the diffuse line.  A diffuse lane
+            // runs its earlier operations on its earlier values; so does a
+            // reflecting lane (vv 0 + d 1 is d, then fma(nn, -2 kn, d)), the
+            // mirror spheres' lanes included; a refracting lane rounds the
+            // same vector differently (three roundings either way).  ratio
+            // cthG - s3 does not cancel: entering (ratio 0.5) ratio cthG <=
+            // 0.5 and s3 = sqrt(1 - sin^2 theta / 4) >= 0.866; leaving
+            // (ratio 2) a lane refracts only where 2 sin theta <= 1, so
+            // ratio cthG >= 1.732 and s3 <= 1.
+            const float rsel = spec ? 1.0f : r1;  // spec is final here
+            v1 = mk3(v1raw.x * rsel, v1raw.y * rsel, v1raw.z * rsel);
+            // (nn and v1 are unit and v1.nn = -cos theta, so |r_out_perp|^2 =
+            // ratio^2 (1 - cos^2 theta) = rs2^2 -- one fma for the dot and
+            // its subtraction, r_out_perp itself never formed.  The one
+            // assumption added: cthG is the un-clamped x0 wherever the clamp
+            // does not bind, which is where s2^2 is 1 - x0^2; then rs2^2 and
+            // |r_out_perp|^2 differ by roundings only.  Where it binds,
+            // cthG = 1 and s2 = 0: the argument is 1, r_out_perp is within
+            // rounding of 0.)
             const float gq = __builtin_fmaf(-rs2, rs2, 1.0f);
-            s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(gq));
-        } else
-        s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(1.0f - dot3(perp, perp)));
-        if (isD) {  // main.cpp:53-55 (unit by construction, not re-normalised)
-            f3 vv = cross3(nn, v1);
-            float cs = cp * s2, ss = sp * s2;
-            nd = mk3(__builtin_fmaf(nn.x, s3, __builtin_fmaf(vv.x, ss, v1.x * cs)),
-                     __builtin_fmaf(nn.y, s3, __builtin_fmaf(vv.y, ss, v1.y * cs)),
-                     __builtin_fmaf(nn.z, s3, __builtin_fmaf(vv.z, ss, v1.z * cs)));
-        } else
-        {  // refraction, main.cpp:93-96
-            nd = mk3(__builtin_fmaf(nn.x, -s3, perp.x), __builtin_fmaf(nn.y, -s3, perp.y),
-                     __builtin_fmaf(nn.z, -s3, perp.z));
+            const float s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(gq));  // both arguments >= 0
+            const f3 vv = cross3(nn, v1);
+            const float k3r = -(kn + kn), k3t = __builtin_fmaf(ratio, cthG, -s3);
+            const float K3 = isD ? s3 : (spec ? k3r : k3t);
+            const float K2 = isD ? sp * s2 : 0.0f;
+            const float K1 = isD ? cp * s2 : (spec ? 1.0f : ratio);
+            // (written to d itself, whose last reader was v1: formed in
+            // registers of its own, the result took three copies per
+            // iteration to reach the loop-carried d)
+            d = mk3(__builtin_fmaf(nn.x, K3, __builtin_fmaf(vv.x, K2, v1.x * K1)),
+                    __builtin_fmaf(nn.y, K3, __builtin_fmaf(vv.y, K2, v1.y * K1)),
+                    __builtin_fmaf(nn.z, K3, __builtin_fmaf(vv.z, K2, v1.z * K1)));
+            nd = d;
+        } else {
+            const f3 perp = mk3(__builtin_fmaf(nn.x, cthG, v1.x) * ratio, __builtin_fmaf(nn.y, cthG, v1.y) * ratio,
+                                __builtin_fmaf(nn.z, cthG, v1.z) * ratio);
+            const float s3 = Math<kExact>::sqrt(isD ? 1.0f - ra : __builtin_fabsf(1.0f - dot3(perp, perp)));
+            if (isD) {  // main.cpp:53-55 (unit by construction, not re-normalised)
+                f3 vv = cross3(nn, v1);
+                float cs = cp * s2, ss = sp * s2;
+                nd = mk3(__builtin_fmaf(nn.x, s3, __builtin_fmaf(vv.x, ss, v1.x * cs)),
+                         __builtin_fmaf(nn.y, s3, __builtin_fmaf(vv.y, ss, v1.y * cs)),
+                         __builtin_fmaf(nn.z, s3, __builtin_fmaf(vv.z, ss, v1.z * cs)));
+            } else {  // refraction, main.cpp:93-96
+                nd = mk3(__builtin_fmaf(nn.x, -s3, perp.x), __builtin_fmaf(nn.y, -s3, perp.y),
+                         __builtin_fmaf(nn.z, -s3, perp.z));
+            }
         }
         }
 #if PTG_BLOCK_STATS == 3
@@ -1253,12 +1296,22 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         }
 #endif
     }
+    // fast mode: the block above formed the reflecting lanes' direction as
+    // well, so the mirror's own code is that block's wave-uniform else -- a
+    // wave of mirror lanes only (frequent in box_mirror's tube of mirror
+    // walls); box waves never execute it
+    if (kExact || !dg_wave)
     if (spec) {  // main.cpp:60-67 (fuzz draw consumed, multiplied by 0)
         PTG_STAT(5);
+        // (fast mode: an empty statement that the compiler may not execute
+        // speculatively -- without it the two tests above are folded into
+        // one select and every wave runs this block's arithmetic again)
+        if constexpr (!kExact)
+            asm volatile("");
         // (fast mode: on the facing normal nn = +-on, its dot kn)
         float k = !kExact ? kn : dot3(on, d);
         k = k + k;
-        // (the reflection's draw after a Fresnel draw: taken in the Fresnel block)
+        // (the reflection's draw after a Fresnel draw: the block's shared second step)
         const f3 rn = !kExact ? nn : on;
         nd = mk3(__builtin_fmaf(-k, rn.x, d.x), __builtin_fmaf(-k, rn.y, d.y), __builtin_fmaf(-k, rn.z, d.z));
     }
