@@ -138,6 +138,11 @@ struct KArgs {
     float *out;
     unsigned long long *acc;  // slab_rows * W * lanes_per_pixel * 3 exact sums
     unsigned long long *segments;
+    // PTG_FLAG_LIGHT_SAMPLING (appended: the fields above keep their offsets):
+    // the scene's light list; n_lights is 0 in a launch without the flag
+    // (plan_frame), which then runs the plain kernels
+    const LightRec *lights;
+    int n_lights;
 };
 
 }  // namespace

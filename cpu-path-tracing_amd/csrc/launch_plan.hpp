@@ -121,6 +121,8 @@ inline void plan_frame(const ptg_params *p, int s_begin, int s_end, KArgs &A)
     A.exact_math = (p->flags & PTG_FLAG_EXACT_MATH) != 0;
     if (!A.exact_math && !A.box_walls_out)
         A.box_mode = 0;  // the fast mode's box-mode wall test assumes rays outside the walls
+    if (!(p->flags & PTG_FLAG_LIGHT_SAMPLING))
+        A.n_lights = 0;  // (the scene's list stays in the context's base)
     A.n_groups = A.slab_rows * A.waves_per_row;
 }
 

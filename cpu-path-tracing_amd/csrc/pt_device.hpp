@@ -242,5 +242,14 @@ struct LinRec {
     GeoRec g;
     ShadeRec s;
 };
+// Light sampling (PTG_FLAG_LIGHT_SAMPLING; scene_prep.hpp light_list_of): one
+// record per listed emitter, 32 B, in scene index order:
+//   c = {C.xyz, R^2}, e = {emission.xyz, id} -- id (integer bits) is what the
+//   scan reports for the sphere: its scan position (linear scenes) or its
+//   scene index (BVH scenes)
+constexpr int kMaxLights = 16;
+struct LightRec {
+    float4 c, e;
+};
 
 }  // namespace ptg

@@ -1058,30 +1058,81 @@ __device__ __forceinline__ int scene_scan_bvh(const KArgs &A, f3 o, f3 d, float 
 // its radiance.
 // shade(): everything after the scene scan -- sky on a miss, else hit
 // record, emission, Russian roulette, BRDF sampling of the next ray.
+//
+// Light sampling (kLS; PTG_FLAG_LIGHT_SAMPLING, include/ptgpu.h): a diffuse
+// hit may be followed by a shadow segment -- one more state of the lane.  The
+// lane keeps the contribution the segment would add, the BRDF direction it
+// resumes with and the light's id in LsLane; the segment's origin is the hit
+// point, which o already holds.  What the lane is doing travels in LsIo: in,
+// this segment is a shadow segment / this hit skips the listed emitters; out,
+// the same two for the lane's next segment (the callers keep them as wave
+// masks).  Without kLS both structs are unused and the code is as before.
+struct LsLane {
+    f3 pend, nd;
+    int light;
+};
+struct LsIo {
+    const LightRec *lights;
+    int n_lights;
+    int hid;                     // what the scan reported (LightRec id)
+    bool shadow, skip;           // in
+    bool to_shadow, skip_next;   // out
+};
+template <bool kExact, bool kLS = false>
+__device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2 *trig, f3 &o, f3 &d, f3 &T, f3 &E,
+                                      int &depth, uint32_t &st, LsLane &ls, LsIo &io);
 template <bool kExact>
 __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2 *trig, f3 &o, f3 &d, f3 &T, f3 &E,
-                                      int &depth, uint32_t &st);
+                                      int &depth, uint32_t &st)
+{
+    LsLane ls;
+    LsIo io;
+    return shade<kExact, false>(hit, t, trig, o, d, T, E, depth, st, ls, io);
+}
 
-template <bool kBvh, bool kExact, bool kCount = false>
+template <bool kBvh, bool kExact, bool kCount = false, bool kLS = false>
 __device__ __forceinline__ bool segment(const KArgs &A, const LinRec *recs, const float2 *trig, f3 &o, f3 &d, f3 &T,
-                                        f3 &E, int &depth, uint32_t &st, ScanCount &cnt)
+                                        f3 &E, int &depth, uint32_t &st, ScanCount &cnt, LsLane &ls, LsIo &io)
 {
     float t;
     const ShadeRec *hit;
     if constexpr (kBvh) {
         const int id = scene_scan_bvh<kCount, kExact>(A, o, d, t, cnt);
         hit = id >= 0 ? A.shade + id : nullptr;
+        if constexpr (kLS)
+            io.hid = id;
     } else {
         const LinRec *w = scene_scan<kExact, kCount>(A, recs, o, d, t, cnt);
         hit = w != recs + A.n ? &w->s : nullptr;
+        if constexpr (kLS)
+            io.hid = (int)(w - recs);
     }
-    return shade<kExact>(hit, t, trig, o, d, T, E, depth, st);
+    return shade<kExact, kLS>(hit, t, trig, o, d, T, E, depth, st, ls, io);
+}
+template <bool kBvh, bool kExact, bool kCount = false>
+__device__ __forceinline__ bool segment(const KArgs &A, const LinRec *recs, const float2 *trig, f3 &o, f3 &d, f3 &T,
+                                        f3 &E, int &depth, uint32_t &st, ScanCount &cnt)
+{
+    LsLane ls;
+    LsIo io;
+    return segment<kBvh, kExact, kCount, false>(A, recs, trig, o, d, T, E, depth, st, cnt, ls, io);
 }
 
-template <bool kExact>
+template <bool kExact, bool kLS>
 __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2 *trig, f3 &o, f3 &d, f3 &T, f3 &E,
-                                      int &depth, uint32_t &st)
+                                      int &depth, uint32_t &st, [[maybe_unused]] LsLane &ls, [[maybe_unused]] LsIo &io)
 {
+    if constexpr (kLS) {
+        // a shadow segment's "shade": the pending value when the light is
+        // the nearest hit, then on with the bounce; depth is not counted
+        if (io.shadow) {
+            const bool lit = io.hid == ls.light;
+            E = mk3(lit ? E.x + ls.pend.x : E.x, lit ? E.y + ls.pend.y : E.y, lit ? E.z + ls.pend.z : E.z);
+            d = ls.nd;
+            io.skip_next = true;
+            return false;
+        }
+    }
     // the segment count first, for every lane: a sky lane's path ends here
     // (its depth is reset by the refill), so the value is only read below --
     // no per-branch copy of the loop-carried register
@@ -1121,6 +1172,16 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         nn = front ? on : mk3(-on.x, -on.y, -on.z);
     }
     // main.cpp:126
+    if constexpr (kLS) {
+        // the hit after a light-sampling step: the listed emitters were
+        // sampled there (their ids by wave-uniform loads)
+        bool listed = false;
+        if (io.skip)
+            for (int k = 0; k < io.n_lights; ++k)
+                listed |= io.hid == __float_as_int(io.lights[k].e.w);
+        if (!listed)
+            E = mk3(__builtin_fmaf(T.x, s1.x, E.x), __builtin_fmaf(T.y, s1.y, E.y), __builtin_fmaf(T.z, s1.z, E.z));
+    } else
     E = mk3(__builtin_fmaf(T.x, s1.x, E.x), __builtin_fmaf(T.y, s1.y, E.y), __builtin_fmaf(T.z, s1.z, E.z));
     // main.cpp:128-139: Russian roulette after depth 4 (the colour row read
     // above by address)
@@ -1148,6 +1209,20 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
     // draw as well: the block's shared second step below (fres_refl).
     // Each lane's draws keep their order and count; killed lanes advance a
     // state their ended path no longer reads.
+    // light sampling: a diffuse lane whose path goes on takes the step's
+    // draws first -- the light (only with several), then u1, u2 -- whatever
+    // the geometry (include/ptgpu.h)
+    [[maybe_unused]] bool ls_run = false;
+    [[maybe_unused]] uint32_t ls_k = 0, ls_m1 = 0, ls_m2 = 0;
+    if constexpr (kLS) {
+        ls_run = isD & (depth < kDepthLimit);
+        uint32_t st_l = st;
+        if (io.n_lights > 1)  // floor(u L) of u = m 2^-24, exactly
+            ls_k = min((uint32_t)(io.n_lights - 1), (draw_bits(st_l) * (uint32_t)io.n_lights) >> 24);
+        ls_m1 = draw_bits(st_l);
+        ls_m2 = draw_bits(st_l);
+        st = ls_run ? st_l : st;
+    }
     const uint32_t m1 = draw_bits(st);
     bool fres_refl = false;  // dielectric lane reflected by its Fresnel draw (isG & fres & reflect)
     // its value u = m1 2^-24, converted once for the diffuse phi (fast
@@ -1315,6 +1390,45 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         const f3 rn = !kExact ? nn : on;
         nd = mk3(__builtin_fmaf(-k, rn.x, d.x), __builtin_fmaf(-k, rn.y, d.y), __builtin_fmaf(-k, rn.z, d.z));
     }
+    if constexpr (kLS) {
+        io.skip_next = ls_run;
+        io.to_shadow = false;
+        if (ls_run) {
+            const LightRec *lr = io.lights + ls_k;
+            const float4 lc = lr->c, le = lr->e;
+            const f3 w = mk3(lc.x - p.x, lc.y - p.y, lc.z - p.z);
+            const float d2 = dot3(w, w);
+            // (a point inside the light, d2 <= R^2, cannot occur in a valid scene: nothing)
+            if (d2 > lc.w && io.hid != __float_as_int(le.w)) {
+                const float q = Math<kExact>::div(lc.w, d2);
+                const float omc = Math<kExact>::div(q, 1.0f + Math<kExact>::sqrt0(1.0f - q));  // 1 - cos theta_max
+                const float a = ((float)ls_m1 * 0x1p-24f) * omc;
+                const float ct = 1.0f - a;
+                const float sth = Math<kExact>::sqrt0(a * (2.0f - a));
+                float cph, sph;
+                Math<kExact>::sincos2pi(ls_m2, trig, cph, sph);
+                const float iw = Math<kExact>::rsqrt(d2);
+                const f3 sw = mk3(w.x * iw, w.y * iw, w.z * iw);
+                // the diffuse sampler's basis rule (main.cpp:52) around sw
+                const f3 su = norm3m<kExact>(__builtin_fabsf(sw.x) > 0.1f ? mk3(sw.z, 0.0f, -sw.x)
+                                                                          : mk3(0.0f, -sw.z, sw.y));
+                const f3 sv = cross3(sw, su);
+                const float kc = cph * sth, ks = sph * sth;
+                const f3 l = mk3(__builtin_fmaf(sw.x, ct, __builtin_fmaf(sv.x, ks, su.x * kc)),
+                                 __builtin_fmaf(sw.y, ct, __builtin_fmaf(sv.y, ks, su.y * kc)),
+                                 __builtin_fmaf(sw.z, ct, __builtin_fmaf(sv.z, ks, su.z * kc)));
+                const float cs = dot3(nn, l);
+                if (cs > 0.0f) {
+                    const float wgt = ((cs + cs) * omc) * (float)io.n_lights;
+                    ls.pend = mk3((T.x * le.x) * wgt, (T.y * le.y) * wgt, (T.z * le.z) * wgt);
+                    ls.nd = nd;
+                    ls.light = __float_as_int(le.w);
+                    nd = l;
+                    io.to_shadow = true;
+                }
+            }
+        }
+    }
     o = p;
     d = nd;
     return killed | (depth >= kDepthLimit);
@@ -1377,7 +1491,13 @@ struct GatherArgs {
     long long max_units;            // the launch covers units [0, min(rec[1], max_units)) ...
     int n_chunks;                   // ... x n_chunks chunks of lvl_chunk[0] samples, chunk-major
 };
-template <bool kCount, bool kBvh, bool kExact, bool kMoments, bool kGather = false>
+//
+// kLS (the ls_* kernels, PTG_FLAG_LIGHT_SAMPLING with a non-empty light list):
+// shade() may turn a lane's next segment into a shadow segment (LsLane, LsIo
+// above).  Two more wave masks carry that state: smask, the lane's next
+// segment is a shadow segment; nmask, its next hit skips the listed emitters.
+// Shadow and bounce segments of different lanes share the scan iterations.
+template <bool kCount, bool kBvh, bool kExact, bool kMoments, bool kGather = false, bool kLS = false>
 __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *const acc2,
                                             const GatherArgs G = GatherArgs{})
 {
@@ -1610,6 +1730,20 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     // radiance parked in the lane's LDS record
     unsigned long long hmask = 0ull, wmask = 0ull, pmask = 0ull;
     auto lane_in = [](unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); };
+    // light sampling: the lane's shadow-segment state and its two masks (a
+    // path that ends leaves both bits clear, so a started path begins clear)
+    [[maybe_unused]] LsLane ls{};
+    [[maybe_unused]] unsigned long long smask = 0ull, nmask = 0ull;
+    auto ls_io = [&]() {  // (at wave level: every lane reads its bits)
+        LsIo io{};
+        if constexpr (kLS) {
+            io.lights = A.lights;
+            io.n_lights = A.n_lights;
+            io.shadow = lane_in(smask);
+            io.skip = lane_in(nmask);
+        }
+        return io;
+    };
     if (item >= 0) {
         f3 ro, rd;
         uint32_t rs;
@@ -1759,11 +1893,19 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
             lin_phase(4);
 #else
             bool done = false;
+            [[maybe_unused]] LsIo io = ls_io();
             if (item >= 0) {
                 PTG_STAT(1);
                 if constexpr (kCount)
                     segs += 1;
+                if constexpr (kLS)
+                    done = segment<kBvh, kExact, kCount, true>(A, recs, trig, o, d, T, E, depth, st, scnt, ls, io);
+                else
                 done = segment<kBvh, kExact, kCount>(A, recs, trig, o, d, T, E, depth, st, scnt);
+            }
+            if constexpr (kLS) {  // every active lane was shaded: its bits anew (idle lanes: clear)
+                smask = __ballot(io.to_shadow);
+                nmask = __ballot(io.skip_next);
             }
             paths_done(__ballot(done));
             refill();
@@ -1890,10 +2032,19 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
             bool done = false;
             const unsigned long long shade_m = rd;
             rd = 0ull;
+            [[maybe_unused]] LsIo io = ls_io();
             if (lane_in(shade_m)) {
                 const int sid = tr.best;
                 const ShadeRec *hrec = sid >= 0 ? A.shade + sid : nullptr;
+                if constexpr (kLS) {
+                    io.hid = sid;
+                    done = shade<kExact, true>(hrec, tr.tb, trig, o, d, T, E, depth, st, ls, io);
+                } else
                 done = shade<kExact>(hrec, tr.tb, trig, o, d, T, E, depth, st);
+            }
+            if constexpr (kLS) {  // the shaded lanes' bits anew; a lane still walking keeps its own
+                smask = (smask & ~shade_m) | __ballot(io.to_shadow);
+                nmask = (nmask & ~shade_m) | __ballot(io.skip_next);
             }
             paths_done(__ballot(done));
             PTG_PHASE(3);
@@ -2034,6 +2185,28 @@ __global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void gather_ker
                                                                                    GatherArgs G)
 {
     render_unit<kCount, kBvh, kExact, true, true>(A, acc2, G);
+}
+
+// PTG_FLAG_LIGHT_SAMPLING with a non-empty light list: the three kernels
+// above with render_unit's kLS.  The shadow-segment state (7 VGPRs) does not
+// fit the one-shot kernel's 64-VGPR budget, so all three take the moments
+// kernels' 6 waves per SIMD (80 VGPRs; DESIGN.md "Light sampling").  Kernels
+// of their own, so the plain kernels keep their names and their code.
+template <bool kCount, bool kBvh, bool kExact>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void render_ls(KArgs A)
+{
+    render_unit<kCount, kBvh, kExact, false, false, true>(A, nullptr);
+}
+template <bool kBvh, bool kExact, bool kCount = false>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void moments_ls(KArgs A, unsigned long long *acc2)
+{
+    render_unit<kCount, kBvh, kExact, true, false, true>(A, acc2);
+}
+template <bool kBvh, bool kExact, bool kCount = false>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void gather_ls(KArgs A, unsigned long long *acc2,
+                                                                               GatherArgs G)
+{
+    render_unit<kCount, kBvh, kExact, true, true, true>(A, acc2, G);
 }
 
 // The pixel value from the exact sums g of its sub-pixels after samps samples
@@ -2496,7 +2669,7 @@ __global__ __launch_bounds__(256) void bump_counts_kernel(int W, const int4 *__r
 }
 
 // Parity probe: one path per record {x, y, sx, sy, sample}.
-template <bool kBvh, bool kExact>
+template <bool kBvh, bool kExact, bool kLS = false>
 __global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32_t *coords, int n, float *out,
                                                          int32_t *segs_out)
 {
@@ -2518,9 +2691,19 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32
     f3 T = mk3(1.0f, 1.0f, 1.0f), E = mk3(0.0f, 0.0f, 0.0f);
     int depth = 0, segs = 0;
     bool done = false;
+    [[maybe_unused]] LsLane ls{};
+    [[maybe_unused]] LsIo io{};
     while (!done) {
         segs += 1;
         ScanCount scnt;
+        if constexpr (kLS) {  // (shadow segments are scans too)
+            io.lights = A.lights;
+            io.n_lights = A.n_lights;
+            io.shadow = io.to_shadow;
+            io.skip = io.skip_next;
+            io.to_shadow = io.skip_next = false;
+            done = segment<kBvh, kExact, false, true>(A, A.lin, A.trig, o, d, T, E, depth, st, scnt, ls, io);
+        } else
         done = segment<kBvh, kExact>(A, A.lin, A.trig, o, d, T, E, depth, st, scnt);
     }
     out[3 * i + 0] = E.x;
@@ -2611,6 +2794,11 @@ struct ptg_context {
     bool uniform_pass;      // a ptg_accumulate_device pass since the last reset: no adaptive entry point
     bool adaptive_pass;     // a ptg_accumulate_active_device pass since the last reset: no uniform n describes the sums
     long long adaptive_added;  // the adds since the last reset: no count is above their sum
+    // PTG_FLAG_LIGHT_SAMPLING: the scene's light list (scene indices; more than kMaxLights: the flag is
+    // refused) and its device records (base.lights, base.n_lights)
+    int n_lights;
+    int light_ids[kMaxLights];
+    LightRec *d_lights;
 };
 
 namespace {
@@ -2749,6 +2937,24 @@ int ptg_context_create(const ptg_sphere *spheres, size_t n_spheres, const ptg_ca
         rc = upload(ctx->d_sph64, spheres, (size_t)n * sizeof(ptg_sphere), "the scene (f64)");
     if (!rc && !linear)
         rc = upload(ctx->d_bvh, bvh.blob.data(), bvh.blob.size(), "the BVH");
+    // the light list (light sampling); too long a list is refused where the flag is given
+    const std::vector<int> light_ids = light_list_of(spheres, n, cam);
+    ctx->n_lights = (int)light_ids.size();
+    if (!rc && ctx->n_lights > 0 && ctx->n_lights <= kMaxLights) {
+        std::vector<int> id_of(n);
+        for (int i = 0; i < n; ++i)
+            id_of[i] = i;
+        if (linear) {  // the scan reports scan positions
+            KArgs scratch{};
+            const std::vector<int> order = scan_order_of(spheres, n, cam, sc, scratch);
+            for (int j = 0; j < n; ++j)
+                id_of[order[j]] = j;
+        }
+        const std::vector<LightRec> lrecs = light_records(spheres, light_ids, id_of);
+        for (int k = 0; k < ctx->n_lights; ++k)
+            ctx->light_ids[k] = light_ids[k];
+        rc = upload(ctx->d_lights, lrecs.data(), lrecs.size() * sizeof(LightRec), "the light list");
+    }
     if (rc) {
         ptg_context_destroy(ctx);
         return rc;
@@ -2759,6 +2965,8 @@ int ptg_context_create(const ptg_sphere *spheres, size_t n_spheres, const ptg_ca
     A.shade = ctx->d_shade;
     A.n = n;
     A.room_nmr = room_neg_margin(A);
+    A.lights = ctx->d_lights;
+    A.n_lights = ctx->d_lights ? ctx->n_lights : 0;
     if (!linear) {
         const unsigned char *blob = static_cast<const unsigned char *>(ctx->d_bvh);
         A.bvh_qnodes = reinterpret_cast<const uint4 *>(blob + bvh.off_q);
@@ -2802,6 +3010,23 @@ int ptg_scene_layout(const ptg_sphere *spheres, size_t n_spheres, const ptg_came
     return PTG_OK;
 }
 
+int ptg_light_list(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, int32_t *ids, int cap,
+                   int *n_lights)
+{
+    if (!cam || !n_lights || (n_spheres && !spheres) || cap < 0 || (cap && !ids))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_spheres > (size_t)(1 << 24))
+        return fail(PTG_ERR_UNSUPPORTED, "too many spheres");
+    const std::vector<int> list = light_list_of(spheres, (int)n_spheres, cam);
+    *n_lights = (int)list.size();
+    for (int k = 0; k < cap && k < (int)list.size(); ++k)
+        ids[k] = list[k];
+    if ((int)list.size() > kMaxLights)
+        return fail(PTG_ERR_UNSUPPORTED, "light sampling: " + std::to_string(list.size()) +
+                                             " small emitters, at most " + std::to_string(kMaxLights));
+    return PTG_OK;
+}
+
 int ptg_context_destroy(ptg_context *ctx)
 {
     if (!ctx)
@@ -2821,6 +3046,8 @@ int ptg_context_destroy(ptg_context *ctx)
         (void)hipFree(ctx->d_acc2);
     if (ctx->d_sph64)
         (void)hipFree(ctx->d_sph64);
+    if (ctx->d_lights)
+        (void)hipFree(ctx->d_lights);
     for (void *q : {(void *)ctx->d_counts, (void *)ctx->d_over, (void *)ctx->d_list, (void *)ctx->d_row_count,
                     (void *)ctx->d_row_unit0, (void *)ctx->d_units, (void *)ctx->d_rec})
         if (q)
@@ -2930,6 +3157,15 @@ int refuse_after_uniform(const ptg_context *ctx, const char *who)
     return PTG_OK;
 }
 
+// PTG_FLAG_LIGHT_SAMPLING on a scene with more small emitters than the light list holds
+int check_lights(const ptg_context *ctx, const ptg_params *p)
+{
+    if ((p->flags & PTG_FLAG_LIGHT_SAMPLING) && ctx->n_lights > kMaxLights)
+        return fail(PTG_ERR_UNSUPPORTED, "light sampling: " + std::to_string(ctx->n_lights) +
+                                             " small emitters, at most " + std::to_string(kMaxLights));
+    return PTG_OK;
+}
+
 // The device entry points' common start, after their argument checks: the
 // context's device current and the launch plan for samples [s_begin, s_end);
 // with_acc: the exact accumulator at the plan's size as well.
@@ -2937,7 +3173,9 @@ int begin_launch(ptg_context *ctx, const ptg_params *p, KArgs &A, int &grid, hip
                  int s_begin = 0, int s_end = -1, bool accumulate_only = false)
 {
     PTG_HIP(hipSetDevice(ctx->device));
-    const int rc = fill_launch(ctx->base, ctx->wave_slots, p, A, grid, s_begin, s_end, accumulate_only);
+    int rc = check_lights(ctx, p);
+    if (!rc)
+        rc = fill_launch(ctx->base, ctx->wave_slots, p, A, grid, s_begin, s_end, accumulate_only);
     return rc || !with_acc ? rc : ensure_acc(ctx, acc_elems_for(A), s);
 }
 
@@ -2948,8 +3186,25 @@ int launch_render(const KArgs &A, int grid, bool count, hipStream_t s, unsigned 
     const bool bvh = A.n > kLinearMax;
     const size_t lds = bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
     // the exact mode's sin/cos table has its own LDS (render_kernel)
-    const int sel = (acc2 ? 8 : 0) | (count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0);
+    // light sampling with lights to sample (n_lights is 0 without the flag): the ls kernels
+    const int sel = (A.n_lights > 0 ? 16 : 0) | (acc2 ? 8 : 0) | (count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0);
     switch (sel) {
+    case 24: moments_ls<false, false, false><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 25: moments_ls<false, true, false><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 26: moments_ls<true, false, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 27: moments_ls<true, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 28: moments_ls<false, false, true><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 29: moments_ls<false, true, true><<<grid, kBlock, lds, s>>>(A, acc2); break;
+    case 30: moments_ls<true, false, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 31: moments_ls<true, true, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
+    case 16: render_ls<false, false, false><<<grid, kBlock, lds, s>>>(A); break;
+    case 17: render_ls<false, false, true><<<grid, kBlock, lds, s>>>(A); break;
+    case 18: render_ls<false, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A); break;
+    case 19: render_ls<false, true, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A); break;
+    case 20: render_ls<true, false, false><<<grid, kBlock, lds, s>>>(A); break;
+    case 21: render_ls<true, false, true><<<grid, kBlock, lds, s>>>(A); break;
+    case 22: render_ls<true, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A); break;
+    case 23: render_ls<true, true, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A); break;
     case 8: moments_kernel<false, false, false><<<grid, kBlock, lds, s>>>(A, acc2); break;
     case 9: moments_kernel<false, true, false><<<grid, kBlock, lds, s>>>(A, acc2); break;
     case 10: moments_kernel<true, false, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2); break;
@@ -2995,6 +3250,9 @@ int launch_ref64(const ptg_context *ctx, const KArgs &A, double *out64, float *o
     R.out64 = out64;
     R.out32 = out32;
     R.segments = d_segments;
+    R.n_lights = A.n_lights;  // (0 without PTG_FLAG_LIGHT_SAMPLING: plan_frame)
+    for (int k = 0; k < A.n_lights; ++k)
+        R.lights[k] = ctx->light_ids[k];
     const long long waves = (long long)A.slab_rows * A.waves_per_row;
     const long long blocks = (waves + 3) / 4;
     if (blocks > 0x7FFFFFFFLL)
@@ -3011,7 +3269,15 @@ int launch_gather(const KArgs &A, int grid, bool count, hipStream_t s, unsigned 
         return PTG_OK;
     const bool bvh = A.n > kLinearMax;
     const size_t lds = bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
-    switch ((count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0)) {
+    switch ((A.n_lights > 0 ? 8 : 0) | (count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0)) {
+    case 8: gather_ls<false, false, false><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 9: gather_ls<false, true, false><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 10: gather_ls<true, false, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    case 11: gather_ls<true, true, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    case 12: gather_ls<false, false, true><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 13: gather_ls<false, true, true><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
+    case 14: gather_ls<true, false, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
+    case 15: gather_ls<true, true, true><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
     case 0: gather_kernel<false, false, false><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
     case 1: gather_kernel<false, true, false><<<grid, kBlock, lds, s>>>(A, acc2, G); break;
     case 2: gather_kernel<true, false, false><<<grid, PTG_BVH_BLOCK, 0, s>>>(A, acc2, G); break;
@@ -3500,7 +3766,14 @@ int ptg_trace_samples_device(ptg_context *ctx, const ptg_params *params, const i
         return rc;
     int blocks = (int)((n + kTraceBlock - 1) / kTraceBlock);
     const bool bvh = A.n > kLinearMax;
-    if (A.exact_math)
+    if (A.n_lights > 0) {  // light sampling with lights to sample
+        if (A.exact_math)
+            bvh ? trace_kernel<true, true, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs)
+                : trace_kernel<false, true, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
+        else
+            bvh ? trace_kernel<true, false, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs)
+                : trace_kernel<false, false, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
+    } else if (A.exact_math)
         bvh ? trace_kernel<true, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs)
             : trace_kernel<false, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
     else
@@ -3575,7 +3848,7 @@ int ptg_render(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *ca
         return rc;
     KArgs A;  // the frame's plan: the slab's geometry (and the reference-arithmetic mode's launch)
     int grid = 0;
-    if ((rc = fill_launch(ctx->base, ctx->wave_slots, params, A, grid))) {
+    if ((rc = check_lights(ctx, params)) || (rc = fill_launch(ctx->base, ctx->wave_slots, params, A, grid))) {
         ptg_context_destroy(ctx);
         return rc;
     }

@@ -119,10 +119,16 @@ __device__ inline void specular(const Hit &h, d3 d, uint32_t &st, d3 &ro, d3 &rd
     rd = add(refl, mk(f, f, f));
 }
 
-// main.cpp:104-158 for the path starting at (o, d); segs += scene scans
-__device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &st, int &segs)
+// main.cpp:104-158 for the path starting at (o, d); segs += scene scans.
+// n_lights > 0 (PTG_FLAG_LIGHT_SAMPLING, include/ptgpu.h): the light-sampling
+// step at every diffuse hit that continues the path, with the fp32 kernels'
+// draws in their order -- the estimator's definition in double.  lights =
+// scene indices of the listed emitters.
+__device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &st, int &segs, const int *lights = nullptr,
+                              int n_lights = 0)
 {
     d3 E = mk(0, 0, 0), T = mk(1, 1, 1);
+    bool skip = false;  // this hit follows a light-sampling step: the listed emitters' emission is not added
     for (int depth = 0; depth < kDepthLimit; ++depth) {
         double t = 0.0;
         segs += 1;
@@ -136,7 +142,12 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
         const ptg_sphere &obj = s[id];
         const Hit h = hit_record(obj, o, d, t);
         d3 color = ld(obj.color);
-        E = add(E, blend(T, ld(obj.emission)));  // main.cpp:126
+        bool listed = false;
+        for (int k = 0; skip && k < n_lights; ++k)
+            listed = listed || lights[k] == id;
+        skip = false;
+        if (!listed)
+            E = add(E, blend(T, ld(obj.emission)));  // main.cpp:126
         double p = color.x;                        // main.cpp:128: std::max({x, y, z})
         if (p < color.y)
             p = color.y;
@@ -150,6 +161,34 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
         }
         T = blend(T, color);
         if (obj.material == PTG_DIFFUSE) {  // main.cpp:44-58
+            if (n_lights > 0 && depth + 1 < kDepthLimit) {  // the path goes on: sample a light first
+                int k = 0;
+                if (n_lights > 1) {
+                    k = (int)floor(draw(st) * n_lights);
+                    k = k < n_lights - 1 ? k : n_lights - 1;
+                }
+                const double u1 = draw(st), u2 = draw(st);
+                const ptg_sphere &lt = s[lights[k]];
+                const d3 w = sub(ld(lt.position), h.p);
+                const double d2 = dot(w, w), R2 = lt.radius * lt.radius;
+                if (d2 > R2 && id != lights[k]) {
+                    const double q = R2 / d2;
+                    const double omc = q / (1.0 + sqrt(1.0 - q));  // 1 - cos theta_max
+                    const double a = u1 * omc, ct = 1.0 - a, sn = sqrt(a * (2.0 - a)), ph = 2 * kPi * u2;
+                    const d3 sw = norm(w);
+                    const d3 su = norm(cross(fabs(sw.x) > 0.1 ? mk(0, 1, 0) : mk(1, 0, 0), sw));
+                    const d3 sv = cross(sw, su);
+                    const d3 l = add(add(mul(mul(su, cos(ph)), sn), mul(mul(sv, sin(ph)), sn)), mul(sw, ct));
+                    const double cs = dot(h.n, l);
+                    if (cs > 0) {  // the shadow segment: an ordinary scan from the hit point
+                        double ts = 0.0;
+                        segs += 1;
+                        if (scene_intersect(s, n, h.p, l, ts) == lights[k])
+                            E = add(E, mul(blend(T, ld(lt.emission)), cs * 2.0 * omc * n_lights));
+                    }
+                }
+                skip = true;
+            }
             const double phi = 2 * kPi * draw(st);
             const double ra = draw(st);
             const double sth = sqrt(ra), cth = sqrt(1.0 - ra);
@@ -195,6 +234,8 @@ struct Args {
     double *out64;  // slab of doubles (ptg_render) or
     float *out32;   // floats (ptg_render_device)
     unsigned long long *segments;
+    int n_lights;  // PTG_FLAG_LIGHT_SAMPLING: the light list (scene indices), 0 without the flag
+    int lights[kMaxLights];
 };
 
 // One lane per sub-pixel: render_subpixel (main.cpp:179-197) for all samples.
@@ -240,7 +281,7 @@ __global__ __launch_bounds__(256) void render_kernel(Args A)
             const d3 dir = sub(sub(add(add(ld(C.lower_left_corner), mul(ld(C.cam_x_axis), s)), mul(ld(C.cam_y_axis), t)),
                                    ld(C.position)),
                                off);
-            const d3 c = radiance(A.spheres, A.n, add(ld(C.position), off), dir, st, segs);
+            const d3 c = radiance(A.spheres, A.n, add(ld(C.position), off), dir, st, segs, A.lights, A.n_lights);
             acc = add(acc, mul(c, 1.0 / A.samps));  // main.cpp:192
         }
     }

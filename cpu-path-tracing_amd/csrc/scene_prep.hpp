@@ -418,6 +418,37 @@ inline std::vector<LinRec> prepare_linear_upload(const ptg_sphere *s, int n, con
     return lin;
 }
 
+// Light sampling (PTG_FLAG_LIGHT_SAMPLING): the scene indices of the spheres
+// with an emission component > 0 that are not huge, ascending.  Huge
+// emitters (and the sky) stay BRDF-sampled only.
+inline std::vector<int> light_list_of(const ptg_sphere *s, int n, const ptg_camera *cam)
+{
+    std::vector<int> ids;
+    for (int i = 0; i < n; ++i)
+        if ((s[i].emission[0] > 0.0 || s[i].emission[1] > 0.0 || s[i].emission[2] > 0.0) && !is_huge(s[i], cam))
+            ids.push_back(i);
+    return ids;
+}
+
+// Their device records.  id_of[i] = what the scan reports for scene index i
+// (linear scenes: its scan position; BVH scenes: i itself).
+inline std::vector<LightRec> light_records(const ptg_sphere *s, const std::vector<int> &ids,
+                                           const std::vector<int> &id_of)
+{
+    std::vector<LightRec> recs;
+    for (int i : ids) {
+        const int32_t id = id_of[i];
+        float idf;
+        std::memcpy(&idf, &id, 4);
+        LightRec r;
+        r.c = make_float4((float)s[i].position[0], (float)s[i].position[1], (float)s[i].position[2],
+                          (float)(s[i].radius * s[i].radius));
+        r.e = make_float4((float)s[i].emission[0], (float)s[i].emission[1], (float)s[i].emission[2], idf);
+        recs.push_back(r);
+    }
+    return recs;
+}
+
 // The camera fields of KArgs (camera.cpp:32-38): pos, base = llc - pos, X, Y, lens radius.
 inline void prepare_camera(const ptg_camera *cam, KArgs &A)
 {

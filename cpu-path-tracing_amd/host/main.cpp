@@ -6,6 +6,7 @@
 //   pt_render_gpu [--spp N] [--scene NAME|FILE] [--width W] [--height H] [--seed S]
 //                 [--devices 0,1,...] [--out FILE] [--format p3|p6]
 //                 [--save-scene FILE] [--dump-json FILE] [--no-render] [--exact-math]
+//                 [--light-sampling]
 //                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]
 //                  [--adaptive [--dilate D] [--spp-map FILE]]]
 //
@@ -20,6 +21,13 @@
 //            (main.cpp:240-247, utils.cpp:11-16)
 //   --exact-math  the kernel's exact arithmetic (PTG_FLAG_EXACT_MATH): the image equals
 //            the CPU oracle's bit for bit (default: the GPU's fast transcendentals)
+//   --light-sampling  next-event estimation (PTG_FLAG_LIGHT_SAMPLING): every diffuse hit also
+//            samples one of the scene's small emissive spheres (at most 16) with a shadow
+//            ray -- several times less noise per sample where such lamps light the scene, so
+//            --noise-target and --adaptive stop earlier; combines with --exact-math,
+//            --noise-target, --adaptive and --devices.  Unbiased like the default, but the
+//            written image clamps sub-pixel means to [0, 1], which clips the default's
+//            brighter outliers more often: images of the two differ slightly in the mean.
 //   --noise-target R  render until converged (ptg_render_to_noise): passes of min-spp,
 //            2 min-spp, 4 min-spp, ... samples per pixel (default 64), at most --spp; stop
 //            when at most the fraction Q (default 0.01) of the pixels has a relative
@@ -175,6 +183,8 @@ int main(int argc, char *argv[])
                 render = false;
             else if (a == "--exact-math")
                 flags |= PTG_FLAG_EXACT_MATH;
+            else if (a == "--light-sampling")
+                flags |= PTG_FLAG_LIGHT_SAMPLING;
             else if (a == "--noise-target") {
                 to_noise = true;
                 target.rel_error = std::atof(val().c_str());

@@ -30,6 +30,7 @@ EXPORTS = (
     "ptg_multi_noise", "ptg_multi_set_active_mask", "ptg_multi_select_active", "ptg_multi_accumulate_active",
     "ptg_multi_resolve_active", "ptg_multi_read_sample_counts", "ptg_multi_render_to_noise",
     "ptg_multi_render_adaptive", "ptg_render_to_noise_multi", "ptg_render_adaptive_multi",
+    "ptg_light_list",
 )
 
 
@@ -108,6 +109,7 @@ def lib():
             "ptg_accumulate_device": (I, [P, C.POINTER(Params), C.c_int32, C.c_int32, P, P]),
             "ptg_resolve_device": (I, [P, C.POINTER(Params), C.c_int32, P, P]),
             "ptg_scene_layout": (I, [P, C.c_size_t, P, P, P]),
+            "ptg_light_list": (I, [P, C.c_size_t, P, P, I, C.POINTER(C.c_int)]),
             "ptg_render_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I, P]),
             "ptg_multi_create": (I, [P, C.c_size_t, P, C.POINTER(C.c_int), I, C.POINTER(C.c_void_p)]),
             "ptg_multi_destroy": (I, [P]),

@@ -52,6 +52,10 @@ FLAG_COUNT_NONFINITE = 2  # include/ptgpu.h PTG_FLAG_COUNT_NONFINITE (4 counters
 FLAG_REFERENCE_F64 = 4  # include/ptgpu.h PTG_FLAG_REFERENCE_F64: the reference's double arithmetic (parity mode)
 FLAG_EXACT_MATH = 8  # include/ptgpu.h PTG_FLAG_EXACT_MATH: exact sequences, bit for bit the oracle's Mode B
 FLAG_MOMENTS = 16  # include/ptgpu.h PTG_FLAG_MOMENTS: progressive passes also sum second moments (Context.noise)
+# include/ptgpu.h PTG_FLAG_LIGHT_SAMPLING: next-event estimation for the small emissive spheres (light_list).
+# Unbiased like the plain estimator: compare the two on raw sums (Context.read_moments), not on clamped images
+FLAG_LIGHT_SAMPLING = 32
+MAX_LIGHTS = 16  # include/ptgpu.h PTG_MAX_LIGHTS
 
 
 def _n_counters(flags: int) -> int:
@@ -420,6 +424,20 @@ def scene_layout(scn, cam):
     check(lib().ptg_scene_layout(sp.ctypes.data, n, ca.ctypes.data, axis.ctypes.data, order.ctypes.data),
           "ptg_scene_layout")
     return axis[:n].tolist(), order[:n].tolist()
+
+
+def light_list(scn, cam):
+    """FLAG_LIGHT_SAMPLING's light list (ptg_light_list, no device needed):
+    the scene indices of the emissive spheres that are not huge, ascending.
+    More than MAX_LIGHTS of them raises PtgError (PTG_ERR_UNSUPPORTED), as
+    rendering the scene with the flag does."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    ids = np.zeros(MAX_LIGHTS, dtype=np.int32)
+    n = C.c_int(0)
+    check(lib().ptg_light_list(sp.ctypes.data, len(sp), ca.ctypes.data, ids.ctypes.data, MAX_LIGHTS, C.byref(n)),
+          "ptg_light_list")
+    return ids[:n.value].tolist()
 
 
 class Context:

@@ -128,6 +128,43 @@ typedef struct ptg_params {
  * to 2^30), the product one fp32 multiply -- the input of ptg_noise_device.
  * The image is not affected.  No effect outside ptg_accumulate_device. */
 #define PTG_FLAG_MOMENTS 16
+/* PTG_FLAG_LIGHT_SAMPLING: next-event estimation for small emissive spheres
+ * (smallpt's "explicit" scheme).  Without the flag nothing changes: the same
+ * draws, the same images.  Honoured by every entry point that renders
+ * (one-shot, progressive with or without PTG_FLAG_MOMENTS, adaptive,
+ * render_to_noise, trace_samples, the ptg_multi_* family, and
+ * PTG_FLAG_REFERENCE_F64, which runs the same estimator in double).
+ *
+ * Light list (ptg_light_list): every sphere with an emission component > 0
+ * that is not "huge" (radius >= 1000, or plane-like for the camera), any
+ * material, in scene index order; at most 16 (more: PTG_ERR_UNSUPPORTED from
+ * the entry points given the flag).  With no light the frame equals the frame
+ * without the flag bit for bit.
+ *
+ * At a diffuse hit that continues the path (point p, facing normal nn, T
+ * already multiplied by the hit's colour), with L > 0 lights, BEFORE the
+ * BRDF's two draws:
+ *   1. L > 1: one draw u picks light k = min(L - 1, floor(u L)); L = 1: no draw
+ *   2. two draws u1, u2 (always, whatever the geometry)
+ *   3. w = C_k - p, d2 = w.w; if d2 > R^2 and the hit sphere is not light k:
+ *        q = R^2 / d2, omc = q / (1 + sqrt(1 - q))      (1 - cos theta_max)
+ *        a = u1 omc, ct = 1 - a, st = sqrt(a (2 - a)), phi = 2 pi u2
+ *        sw = w / |w|, su = norm((|sw.x| > 0.1 ? y : x) x sw), sv = sw x su
+ *        l = su cos(phi) st + sv sin(phi) st + sw ct,  cs = nn.l
+ *        if cs > 0: a shadow segment, an ordinary nearest-hit scan from p
+ *        along l (counted like any scan); if its winner is light k:
+ *        E += T * Le_k * (cs 2 omc L)
+ *   4. the path's next hit skips the emission of the spheres on the light
+ *      list (that one hit only; also when step 3 added nothing).  After a
+ *      mirror or dielectric bounce and at the camera ray emission counts as
+ *      without the flag; huge emitters and the sky always count.
+ * Both estimators are unbiased for the same integral, so their RAW means
+ * agree; the image clamps every sub-pixel mean to [0, 1], and the plain
+ * estimator's heavier tails are clipped more often -- clamped images of
+ * bright scenes (simple_scene) therefore differ slightly in the mean between
+ * the two.  Compare estimators on the raw sums (ptg_read_moments_device). */
+#define PTG_FLAG_LIGHT_SAMPLING 32
+#define PTG_MAX_LIGHTS 16
 
 typedef struct ptg_context ptg_context;
 
@@ -522,6 +559,14 @@ int ptg_tonemap_device(const float *d_image, uint8_t *d_out, size_t count, void 
  * candidate roots go to the sphere tested first. */
 int ptg_scene_layout(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, int32_t *anchor_axis,
                      int32_t *scan_order);
+
+/* PTG_FLAG_LIGHT_SAMPLING's light list, host only: the scene indices of the
+ * emissive spheres that are not huge, ascending.  *n_lights receives their
+ * number; ids (cap entries, may be NULL when cap is 0) the first
+ * min(cap, *n_lights) of them.  More than PTG_MAX_LIGHTS: *n_lights is set
+ * and the call returns PTG_ERR_UNSUPPORTED, as rendering with the flag does. */
+int ptg_light_list(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, int32_t *ids, int cap,
+                   int *n_lights);
 
 /* Parity probe: trace individual samples.  d_coords holds n records
  * {x, y, sx, sy, sample} (int32 each); d_out n*3 floats (radiance of that
