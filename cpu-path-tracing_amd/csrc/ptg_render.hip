@@ -2712,6 +2712,66 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32
     segs_out[i] = segs;
 }
 
+// ptg_features_device: the first hit of the pixel's nsub^2 deterministic
+// camera rays (camera_ray with both jitter draws 0.5 and no lens offset), by
+// the renderer's own scan in exact arithmetic; one thread per slab pixel.
+// 12 floats: {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0} (include/ptgpu.h).
+template <bool kBvh>
+__global__ __launch_bounds__(256) void features_kernel(KArgs A, float4 *__restrict__ feat)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)A.slab_rows * A.W)
+        return;
+    const int slab_row = (int)(i / A.W);
+    const int r = out_row_of(A, slab_row);
+    if (r >= A.H)
+        return;
+    const int px = (int)(i - (long long)slab_row * A.W);
+    const int y = A.H - 1 - r;  // main.cpp:181
+    const CamC C = cam_of(A);
+    const f3 o = mk3(C.p.x, C.p.y, C.p.z);
+    f3 n = mk3(0.0f, 0.0f, 0.0f), P = n, a = n;
+    float z = 0.0f;
+    int hits = 0;
+    for (int sy = 0; sy < A.nsub; ++sy)
+        for (int sx = 0; sx < A.nsub; ++sx) {
+            const float xin = __builtin_fmaf(C.b.w, 0.5f, (float)px + (float)sx * C.b.w);
+            const float yin = __builtin_fmaf(C.b.w, 0.5f, (float)y + (float)sy * C.b.w);
+            const float fs = xin * C.X.w;
+            const float ft = yin * C.Y.w;
+            const f3 d = mk3(__builtin_fmaf(C.Y.x, ft, __builtin_fmaf(C.X.x, fs, C.b.x)),
+                             __builtin_fmaf(C.Y.y, ft, __builtin_fmaf(C.X.y, fs, C.b.y)),
+                             __builtin_fmaf(C.Y.z, ft, __builtin_fmaf(C.X.z, fs, C.b.z)));
+            float t;
+            ScanCount cnt;
+            const ShadeRec *hit;
+            if constexpr (kBvh) {
+                const int id = scene_scan_bvh<false, true>(A, o, d, t, cnt);
+                hit = id >= 0 ? A.shade + id : nullptr;
+            } else {
+                const LinRec *w = scene_scan<true>(A, A.lin, o, d, t, cnt);
+                hit = w != A.lin + A.n ? &w->s : nullptr;
+            }
+            if (!hit)
+                continue;
+            // the hit point and the facing normal as shade<true> forms them
+            const float4 s0 = hit->s0, s2 = hit->s2;
+            const f3 p = mk3(__builtin_fmaf(d.x, t, o.x), __builtin_fmaf(d.y, t, o.y), __builtin_fmaf(d.z, t, o.z));
+            const f3 on = mk3((p.x - s0.x) * s2.w, (p.y - s0.y) * s2.w, (p.z - s0.z) * s2.w);
+            const bool front = dot3(on, d) < 0.0f;
+            hits += 1;
+            n = mk3(n.x + (front ? on.x : -on.x), n.y + (front ? on.y : -on.y), n.z + (front ? on.z : -on.z));
+            P = mk3(P.x + p.x, P.y + p.y, P.z + p.z);
+            a = mk3(a.x + s2.x, a.y + s2.y, a.z + s2.z);
+            z = __builtin_fmaf(t, Math<true>::sqrt(dot3(d, d)), z);
+        }
+    const float k = (float)(hits > 0 ? hits : 1);
+    float4 *out = feat + (size_t)i * 3;
+    out[0] = make_float4(n.x / k, n.y / k, n.z / k, z / k);
+    out[1] = make_float4(P.x / k, P.y / k, P.z / k, (float)hits / (float)A.lanes_per_pixel);
+    out[2] = hits > 0 ? make_float4(a.x / k, a.y / k, a.z / k, 0.0f) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+}
+
 // ptg_math_probe_device: the primitives as the render kernels call them
 template <bool kExact>
 __global__ __launch_bounds__(256) void math_probe_kernel(int op, const float *in, float *out, int n,
@@ -3779,6 +3839,35 @@ int ptg_trace_samples_device(ptg_context *ctx, const ptg_params *params, const i
     else
         bvh ? trace_kernel<true, false><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs)
             : trace_kernel<false, false><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_features_device(ptg_context *ctx, const ptg_params *params, float *d_feat, void *stream)
+{
+    if (!ctx || !d_feat)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: NULL context or output");
+    if (reinterpret_cast<uintptr_t>(d_feat) % 16)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: the output must be 16-byte aligned");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    int grid = 0;
+    // the frame's geometry only: the scan's fields are those of the exact mode whatever the flags
+    ptg_params geo = *params;
+    geo.samples = 1;
+    geo.chunk_samples = 0;
+    geo.flags = PTG_FLAG_EXACT_MATH;
+    if ((rc = begin_launch(ctx, &geo, A, grid, s, /*with_acc=*/false)))
+        return rc;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    const unsigned blocks = (unsigned)((pixels + 255) / 256);
+    if (A.n > kLinearMax)
+        features_kernel<true><<<blocks, 256, 0, s>>>(A, reinterpret_cast<float4 *>(d_feat));
+    else
+        features_kernel<false><<<blocks, 256, 0, s>>>(A, reinterpret_cast<float4 *>(d_feat));
     PTG_HIP(hipGetLastError());
     return PTG_OK;
 }

@@ -9,6 +9,7 @@
 //                 [--light-sampling]
 //                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]
 //                  [--adaptive [--dilate D] [--spp-map FILE]]]
+//                 [--denoise [--denoise-iterations N]] [--features-out PREFIX]
 //
 //   spp      total samples per pixel (main.cpp:206: divided by the 4 sub-pixels), default 4
 //   scene    box_mirror (the reference binary's scene, main.cpp:25,208) | box | simple |
@@ -43,6 +44,19 @@
 //            its own spp.  --spp-map FILE writes the samples per sub-pixel of every pixel as
 //            a binary PGM (P5; 16-bit big-endian values when a count is above 255).  The
 //            "noise:" line then ends with the mean samples per sub-pixel.
+//   --denoise  filter the frame with the variance-guided a-trous filter (ptg_render_denoised:
+//            first-hit features and the per-pixel variance guide it; --denoise-iterations N,
+//            0..8, default 5).  Needs --spp >= 8 (two samples per sub-pixel).  With
+//            --noise-target the filter runs on the frame at the spp the "noise:" line reports
+//            (ptg_render_to_noise_denoised: the passes carry the moments, nothing is rendered
+//            twice).  With --adaptive, or with a --devices list of several: exit status 2
+//            (DESIGN.md "Denoising", out of scope).
+//   --features-out PREFIX  the first-hit features of every pixel (ptg_features; no RNG, the
+//            sub-pixel centres): PREFIX_normal.ppm (P6, round((n + 1) / 2 * 255) per axis, the
+//            mean facing normal; sky 0 0 0 -> 128 128 128), PREFIX_albedo.ppm (P6, round(a * 255),
+//            colours clamped to [0, 1]; sky white) and PREFIX_distance.pgm (P5, 16-bit
+//            big-endian, round(65535 z / z_max) with z_max the frame's largest distance; sky 0).
+//            Written before the frame is rendered, on the first device of --devices.
 //   --save-scene / --dump-json write the scene (scene file) / the scene and the
 //            camera::with_config result (JSON, 17 digits) and need no GPU with --no-render
 #include <chrono>
@@ -98,6 +112,34 @@ std::vector<int> parse_devices(std::string const &s)
     return d;
 }
 
+// --features-out: 12 floats per pixel {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0} as three images
+void write_features(std::string const &prefix, std::vector<float> const &feat, int w, int h)
+{
+    std::size_t const px = static_cast<std::size_t>(w) * h;
+    auto byte = [](double x) {
+        double const c = x < 0.0 ? 0.0 : (1.0 < x ? 1.0 : x);
+        return static_cast<char>(static_cast<unsigned char>(std::round(c * 255.0)));
+    };
+    std::ofstream n{prefix + "_normal.ppm", std::ios::binary}, a{prefix + "_albedo.ppm", std::ios::binary},
+        z{prefix + "_distance.pgm", std::ios::binary};
+    n << "P6\n" << w << ' ' << h << "\n255\n";
+    a << "P6\n" << w << ' ' << h << "\n255\n";
+    z << "P5\n" << w << ' ' << h << "\n65535\n";
+    float zmax = 0.0f;
+    for (std::size_t i = 0; i < px; ++i)
+        zmax = feat[i * 12 + 3] > zmax ? feat[i * 12 + 3] : zmax;
+    for (std::size_t i = 0; i < px; ++i) {
+        float const *f = &feat[i * 12];
+        for (int c = 0; c < 3; ++c) {
+            n.put(byte((double(f[c]) + 1.0) * 0.5));
+            a.put(byte(double(f[8 + c])));
+        }
+        int const v = zmax > 0.0f ? static_cast<int>(std::round(65535.0 * double(f[3]) / double(zmax))) : 0;
+        z.put(static_cast<char>(v >> 8));
+        z.put(static_cast<char>(v & 255));
+    }
+}
+
 void dump_json(pt::scene const &scn, pt::camera const &cam, std::string const &path)
 {
     auto v3 = [](pt::vec3 const &a) {
@@ -136,6 +178,9 @@ int main(int argc, char *argv[])
     bool to_noise = false, adaptive = false;
     int min_spp = 64, dilate = 1;
     std::string spp_map;
+    bool denoise = false;
+    int denoise_iterations = -1;  // -1: the default
+    std::string features_out;
     ptg_noise_target target{};
     target.floor = 0.01;
     target.max_fraction = 0.01;
@@ -200,6 +245,12 @@ int main(int argc, char *argv[])
                 dilate = std::atoi(val().c_str());
             else if (a == "--spp-map")
                 spp_map = val();
+            else if (a == "--denoise")
+                denoise = true;
+            else if (a == "--denoise-iterations")
+                denoise_iterations = std::atoi(val().c_str());
+            else if (a == "--features-out")
+                features_out = val();
             else {
                 std::fprintf(stderr, "unknown option %s\n", a.c_str());
                 return 2;
@@ -215,6 +266,22 @@ int main(int argc, char *argv[])
         return 2;
     }
     int const samps = spp / (num_subpixels * num_subpixels);
+    if (denoise_iterations != -1 && (!denoise || denoise_iterations < 0 || denoise_iterations > 8)) {
+        std::fprintf(stderr, "--denoise-iterations needs --denoise and a value in 0..8\n");
+        return 2;
+    }
+    if (denoise && adaptive) {
+        std::fprintf(stderr, "--denoise does not combine with --adaptive (the pixels hold different sample counts)\n");
+        return 2;
+    }
+    if (denoise && parse_devices(devices).size() != 1) {
+        std::fprintf(stderr, "--denoise renders on one device (--devices %s)\n", devices.c_str());
+        return 2;
+    }
+    if (denoise && render && samps < 2) {
+        std::fprintf(stderr, "--denoise needs --spp >= 8 (two samples per sub-pixel for the variance)\n");
+        return 2;
+    }
 
     pt::scene some_scene;
     std::string err;
@@ -235,9 +302,25 @@ int main(int argc, char *argv[])
     std::vector<pt::vec3> image(static_cast<std::size_t>(width) * height, pt::vec3{0, 0, 0});
     std::vector<int> const devs = parse_devices(devices);
     int const nd = static_cast<int>(devs.size());
+    if (!features_out.empty()) {
+        std::vector<float> feat;
+        int const frc = nd < 1 ? PTG_ERR_INVALID_ARGUMENT
+                               : pt::gpu::feature_frame(some_scene, cam, feat, width, height, num_subpixels, devs[0]);
+        if (frc != PTG_OK) {
+            std::fprintf(stderr, "features failed (%d): %s\n", frc, ptg_last_error());
+            return 1;
+        }
+        write_features(features_out, feat, width, height);
+    }
     auto const t0 = std::chrono::steady_clock::now();
     int rc = PTG_OK;
     int samps_done = samps;
+    // --denoise: the filter's defaults, the pixel spread from the camera
+    ptg_denoise_params dn{};
+    ptg_denoise_defaults(&dn);
+    dn.pixel_spread = 0.0f;
+    if (denoise_iterations >= 0)
+        dn.iterations = denoise_iterations;
     if (to_noise) {  // render until converged: --spp is the most it takes
         if (nd < 1) {
             std::fprintf(stderr, "--devices needs at least one device\n");
@@ -297,10 +380,15 @@ int main(int argc, char *argv[])
             }
         } else {
             ptg_noise_report rep{};
-            rc = nd > 1 ? pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep, devs,
-                                                         num_subpixels, seed, flags)
-                        : pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep,
-                                                         num_subpixels, seed, devs[0], flags);
+            if (denoise)  // (one device: checked above) the frame it stops at, filtered
+                rc = pt::gpu::render_image_to_noise_denoised(some_scene, cam, image, width, height, samps, target, rep,
+                                                             &dn, num_subpixels, seed, devs[0], flags);
+            else if (nd > 1)
+                rc = pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep, devs,
+                                                    num_subpixels, seed, flags);
+            else
+                rc = pt::gpu::render_image_to_noise(some_scene, cam, image, width, height, samps, target, rep,
+                                                    num_subpixels, seed, devs[0], flags);
             if (rc == PTG_OK) {
                 samps_done = rep.samples_done;
                 std::fprintf(stderr,
@@ -311,6 +399,9 @@ int main(int argc, char *argv[])
                              target.rel_error, rep.max_rho, rep.mean_rho, rep.converged);
             }
         }
+    } else if (denoise) {
+        rc = pt::gpu::render_image_denoised(some_scene, cam, image, width, height, samps, &dn, num_subpixels, seed,
+                                            devs[0], flags);
     } else if (nd == 1 && devs[0] < 0) {  // main.cpp:214-236 replaced by one call
         rc = pt::gpu::render_image(some_scene, cam, image, width, height, samps, num_subpixels, seed, -1, flags);
     } else {  // several GPUs of this process: shards + one RCCL gather

@@ -167,5 +167,74 @@ inline int render_image_adaptive(scene const &scn, camera const &cam, std::vecto
                                      sample_counts ? sample_counts->data() : nullptr, &report);
 }
 
+// render_image followed by the variance-guided a-trous filter
+// (ptg_render_denoised): samps >= 2 per sub-pixel, one device.  denoise
+// nullptr: the defaults with the camera's pixel spread; iterations 0 gives
+// render_image's image bit for bit.
+inline int render_image_denoised(scene const &scn, camera const &cam, std::vector<vec3> &image, int width, int height,
+                                 int samps, ptg_denoise_params const *denoise = nullptr, int num_subpixels = 2,
+                                 std::uint64_t seed = default_seed, int device = -1, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return ptg_render_denoised(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                               reinterpret_cast<ptg_camera const *>(&cam), &p, device, denoise,
+                               reinterpret_cast<double *>(image.data()));
+}
+
+// render_image_to_noise whose frame, at the samples it stopped at, goes through
+// the filter (ptg_render_to_noise_denoised; nothing is rendered twice).
+inline int render_image_to_noise_denoised(scene const &scn, camera const &cam, std::vector<vec3> &image, int width,
+                                          int height, int samps, ptg_noise_target const &target,
+                                          ptg_noise_report &report, ptg_denoise_params const *denoise = nullptr,
+                                          int num_subpixels = 2, std::uint64_t seed = default_seed, int device = -1,
+                                          int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return ptg_render_to_noise_denoised(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                                        reinterpret_cast<ptg_camera const *>(&cam), &p, device, &target, denoise,
+                                        reinterpret_cast<double *>(image.data()), &report);
+}
+
+// The first-hit feature frame (ptg_features): width * height * 12 floats in the
+// image's row order, {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0} per pixel.
+inline int feature_frame(scene const &scn, camera const &cam, std::vector<float> &features, int width, int height,
+                         int num_subpixels = 2, int device = -1)
+{
+    features.assign(static_cast<std::size_t>(width) * static_cast<std::size_t>(height) * 12, 0.0f);
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = 1;
+    p.num_subpixels = num_subpixels;
+    p.seed = default_seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    return ptg_features(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                        reinterpret_cast<ptg_camera const *>(&cam), &p, device, features.data());
+}
+
 }  // namespace gpu
 }  // namespace pt

@@ -31,6 +31,8 @@ EXPORTS = (
     "ptg_multi_resolve_active", "ptg_multi_read_sample_counts", "ptg_multi_render_to_noise",
     "ptg_multi_render_adaptive", "ptg_render_to_noise_multi", "ptg_render_adaptive_multi",
     "ptg_light_list",
+    "ptg_features_device", "ptg_denoise_defaults", "ptg_pixel_spread", "ptg_denoise_scratch_bytes",
+    "ptg_denoise_device", "ptg_denoise_host", "ptg_render_denoised", "ptg_render_to_noise_denoised", "ptg_features",
 )
 
 
@@ -79,6 +81,15 @@ class AdaptiveReport(C.Structure):  # ptg_adaptive_report
 
 
 assert C.sizeof(AdaptiveTarget) == 32 and C.sizeof(AdaptiveReport) == 88 + 20 * NOISE_MAX_PASSES
+
+
+class DenoiseParams(C.Structure):  # ptg_denoise_params
+    _fields_ = [("iterations", C.c_int32), ("reserved0_", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float),
+                ("k_plane", C.c_float), ("k_albedo", C.c_float), ("eps_color", C.c_float),
+                ("pixel_spread", C.c_float), ("reserved_", C.c_float * 8)]
+
+
+assert C.sizeof(DenoiseParams) == 64
 
 _lib = None
 
@@ -151,6 +162,20 @@ def lib():
                                               C.POINTER(NoiseTarget), P, C.POINTER(NoiseReport)]),
             "ptg_render_adaptive_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I,
                                               C.POINTER(AdaptiveTarget), P, P, C.POINTER(AdaptiveReport)]),
+            "ptg_features_device": (I, [P, C.POINTER(Params), P, P]),
+            "ptg_denoise_defaults": (I, [C.POINTER(DenoiseParams)]),
+            "ptg_pixel_spread": (I, [P, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+            "ptg_denoise_scratch_bytes": (I, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+            "ptg_denoise_device": (I, [P, P, P, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), P, P, P, C.c_size_t,
+                                       P]),
+            "ptg_denoise_host": (I, [P, P, P, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), P, P]),
+            "ptg_render_denoised": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(DenoiseParams), P]),
+            "ptg_render_to_noise_denoised": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(NoiseTarget),
+                                                 C.POINTER(DenoiseParams), P, C.POINTER(NoiseReport)]),
+            "ptg_features": (I, [P, C.c_size_t, P, C.POINTER(Params), I, P]),
+            # internal (tests, tools): ptg_denoise_device with the kernel named (0 tiled where it fits, 1 plain)
+            "ptg_denoise_device_kernel_": (I, [P, P, P, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), P, P, P,
+                                               C.c_size_t, P, I]),
             "ptg_multi_inject_gather_fault_": (I, [P, I]),
             # internal (tests): n shards on one device, gathered by device copies
             "ptg_multi_create_local_": (I, [P, C.c_size_t, P, I, I, C.POINTER(C.c_void_p)]),

@@ -7,6 +7,9 @@
 * render_to_noise(...),  -- render() that stops when a noise target is met;
   render_adaptive(...)      the adaptive one gives the later passes only to
                             the pixels still over it (a sample count per pixel).
+* render_denoised(...),  -- render() followed by the variance-guided a-trous
+  denoise(...)              filter (first-hit features from Context.features);
+                            denoise() filters device tensors the caller holds.
 * Context                -- device-resident scene for repeated renders into
                             torch CUDA tensors (bench, multi-GPU).
 * render_sharded(...)    -- one process per GPU: each rank renders its
@@ -22,7 +25,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from ._abi import NOISE_MAX_PASSES, AdaptiveReport, AdaptiveTarget, NoiseReport, NoiseTarget, Params, check, lib
+from ._abi import NOISE_MAX_PASSES, AdaptiveReport, AdaptiveTarget, DenoiseParams, NoiseReport, NoiseTarget, Params, check, lib
 from .scene import CAMERA_DT, SPHERE_DT, camera, scene
 
 DEFAULT_SEED = 0x5EED0001
@@ -660,6 +663,22 @@ class Context:
         check(lib().ptg_read_sample_counts_device(self._h, C.byref(params), C.c_void_p(counts.data_ptr()),
                                                   C.c_void_p(self._stream(stream))), "ptg_read_sample_counts_device")
 
+    # ---- denoising (ptg_features_device; the filter itself needs no context: denoise())
+    def features(self, params: Params, out=None, stream=None):
+        """The first-hit features of every slab pixel (float32, slab rows*W*12:
+        {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0}), the guide of denoise().
+        Deterministic camera rays through the renderer's exact scan: no
+        dependence on seed, samples or flags.  Returns `out` ([rows, W, 12]
+        when allocated here)."""
+        import torch
+        rows = shard_rows(params.height, params.band_rows, params.shard_count)
+        if out is None:
+            out = torch.zeros((rows, params.width, 12), dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._check(out, torch.float32, rows * params.width * 12)
+        check(lib().ptg_features_device(self._h, C.byref(params), C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(self._stream(stream))), "ptg_features_device")
+        return out
+
     def trace_samples(self, coords, params: Params):
         """Parity probe: radiance + segment count of individual paths
         (coords: int32 CUDA tensor [n, 5] = x, y, sx, sy, sample)."""
@@ -707,6 +726,139 @@ class Context:
 def _check_tensor(t, dtype, min_numel):
     if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < min_numel:
         raise ValueError(f"expected a contiguous CUDA {dtype} tensor with >= {min_numel} elements")
+
+
+def denoise_defaults() -> DenoiseParams:
+    """ptg_denoise_defaults (host only).  pixel_spread is a generic 1/1024:
+    set it from pixel_spread(cam, width, height)."""
+    k = DenoiseParams()
+    check(lib().ptg_denoise_defaults(C.byref(k)), "ptg_denoise_defaults")
+    return k
+
+
+def pixel_spread(cam, width: int, height: int) -> float:
+    """ptg_pixel_spread (host only): the world size of a pixel at distance 1."""
+    ca = _camera_array(cam)
+    v = C.c_float(0.0)
+    check(lib().ptg_pixel_spread(ca.ctypes.data_as(C.c_void_p), int(width), int(height), C.byref(v)),
+          "ptg_pixel_spread")
+    return v.value
+
+
+def denoise_scratch_bytes(width: int, height: int) -> int:
+    n = C.c_size_t(0)
+    check(lib().ptg_denoise_scratch_bytes(int(width), int(height), C.byref(n)), "ptg_denoise_scratch_bytes")
+    return n.value
+
+
+def denoise(color, var, feat, params: Optional[DenoiseParams] = None, var_out: bool = False, scratch=None,
+            stream=None, kernel_: int = 0):
+    """ptg_denoise_device on whole frames held as torch CUDA tensors: color
+    and var [H, W, 3] float32 (Context.resolve / Context.noise of a
+    shard_count = 1 slab cut to its H rows, or a gathered frame), feat
+    [H, W, 12] (Context.features).  Returns the filtered colour, or (colour,
+    variance) with var_out=True.  `scratch`: a float32 tensor of at least
+    denoise_scratch_bytes(W, H) bytes to reuse (allocated here otherwise; the
+    call itself allocates nothing).  Asynchronous on `stream`.  kernel_ (tests
+    and tools): 1 runs the plain filter kernel at every step instead of the
+    tiled one where its tile fits; the result is the same bit for bit."""
+    import torch
+    if color.dim() != 3 or color.shape[2] != 3:
+        raise ValueError("color must be [H, W, 3]")
+    H, W = int(color.shape[0]), int(color.shape[1])
+    _check_tensor(color, torch.float32, H * W * 3)
+    for t, n in ((var, 3), (feat, 12)):
+        _check_tensor(t, torch.float32, H * W * n)
+        if t.device != color.device or t.numel() != H * W * n:
+            raise ValueError("var must be [H, W, 3] and feat [H, W, 12] on color's device")
+    k = params if params is not None else denoise_defaults()
+    need = denoise_scratch_bytes(W, H)
+    if scratch is None:
+        scratch = torch.empty(need // 4, dtype=torch.float32, device=color.device)
+    _check_tensor(scratch, torch.float32, 0)
+    out = torch.empty_like(color)
+    vout = torch.empty_like(color) if var_out else None
+    s = (stream or torch.cuda.current_stream(color.device)).cuda_stream
+    with torch.cuda.device(color.device):
+        args = (C.c_void_p(color.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(feat.data_ptr()), W, H,
+                C.byref(k), C.c_void_p(out.data_ptr()), C.c_void_p(vout.data_ptr()) if var_out else None,
+                C.c_void_p(scratch.data_ptr()), scratch.numel() * 4, C.c_void_p(s))
+        if kernel_:
+            check(lib().ptg_denoise_device_kernel_(*args, int(kernel_)), "ptg_denoise_device_kernel_")
+        else:
+            check(lib().ptg_denoise_device(*args), "ptg_denoise_device")
+    return (out, vout) if var_out else out
+
+
+def denoise_host(color: np.ndarray, var: np.ndarray, feat: np.ndarray, params: Optional[DenoiseParams] = None,
+                 var_out: bool = False):
+    """ptg_denoise_host: the filter's CPU statement on numpy arrays ([H, W, 3],
+    [H, W, 3], [H, W, 12] float32) -- the same arithmetic, bit for bit."""
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    var = np.ascontiguousarray(var, dtype=np.float32)
+    feat = np.ascontiguousarray(feat, dtype=np.float32)
+    H, W = color.shape[:2]
+    if color.shape != (H, W, 3) or var.shape != (H, W, 3) or feat.shape != (H, W, 12):
+        raise ValueError("color and var must be [H, W, 3], feat [H, W, 12]")
+    k = params if params is not None else denoise_defaults()
+    out = np.empty_like(color)
+    vout = np.empty_like(color) if var_out else None
+    check(lib().ptg_denoise_host(color.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p),
+                                 feat.ctypes.data_as(C.c_void_p), W, H, C.byref(k), out.ctypes.data_as(C.c_void_p),
+                                 vout.ctypes.data_as(C.c_void_p) if var_out else None), "ptg_denoise_host")
+    return (out, vout) if var_out else out
+
+
+def render_denoised(scn, cam, image: np.ndarray, width: int, height: int, samples: int, num_subpixels: int = 2,
+                    seed: int = DEFAULT_SEED, device: int = -1, flags: int = 0,
+                    params: Optional[DenoiseParams] = None) -> np.ndarray:
+    """ptg_render_denoised: render() at `samples` (>= 2) with the moments
+    kept, then the filter guided by the frame's variance and first-hit
+    features; added into `image` like render().  params None: the defaults
+    with the camera's pixel_spread."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    if image.dtype != np.float64 or not image.flags["C_CONTIGUOUS"] or image.size != width * height * 3:
+        raise ValueError("image must be a C-contiguous float64 array of width*height*3 values")
+    p = make_params(width, height, samples, num_subpixels, seed, flags=flags)
+    check(lib().ptg_render_denoised(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
+                                    C.byref(p), int(device), C.byref(params) if params is not None else None,
+                                    image.ctypes.data_as(C.c_void_p)), "ptg_render_denoised")
+    return image
+
+
+def render_to_noise_denoised(scn, cam, image: np.ndarray, width: int, height: int, samples: int, rel_error: float,
+                             floor: float = 0.01, max_fraction: float = 0.01, min_samples: int = 16,
+                             num_subpixels: int = 2, seed: int = DEFAULT_SEED, device: int = -1, flags: int = 0,
+                             params: Optional[DenoiseParams] = None) -> dict:
+    """ptg_render_to_noise_denoised: render_to_noise() whose frame, at the
+    samples it stopped at, goes through the filter (its passes carry the
+    moments: nothing is rendered twice).  Returns render_to_noise()'s report."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    if image.dtype != np.float64 or not image.flags["C_CONTIGUOUS"] or image.size != width * height * 3:
+        raise ValueError("image must be a C-contiguous float64 array of width*height*3 values")
+    p = make_params(width, height, samples, num_subpixels, seed, flags=flags)
+    target = NoiseTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), 0)
+    rep = NoiseReport()
+    check(lib().ptg_render_to_noise_denoised(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
+                                             C.byref(p), int(device), C.byref(target),
+                                             C.byref(params) if params is not None else None,
+                                             image.ctypes.data_as(C.c_void_p), C.byref(rep)),
+          "ptg_render_to_noise_denoised")
+    return _noise_report(rep)
+
+
+def features(scn, cam, width: int, height: int, num_subpixels: int = 2, device: int = -1) -> np.ndarray:
+    """ptg_features: the first-hit feature frame on the host, float32
+    [height, width, 12] in render()'s row order."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    out = np.zeros((height, width, 12), dtype=np.float32)
+    p = make_params(width, height, 1, num_subpixels)
+    check(lib().ptg_features(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p), C.byref(p),
+                             int(device), out.ctypes.data_as(C.c_void_p)), "ptg_features")
+    return out
 
 
 def unshard_device(gathered, image, width, height, band_rows, shard_count, stream=None):

@@ -543,6 +543,110 @@ int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const
                               const ptg_adaptive_target *target, double *image_rgb, int32_t *sample_counts,
                               ptg_adaptive_report *report);
 
+/* ---- denoising (DESIGN.md "Denoising") --------------------------------
+ * An edge-avoiding a-trous filter over a frame, guided by first-hit features
+ * and by the per-pixel variance of ptg_noise_device.  Additive: no draw, image
+ * or plan of the entry points above changes.
+ *
+ * ptg_features_device: 12 floats per slab pixel, in ptg_render_device's slab
+ * layout (slab rows past the image are left untouched): {n.xyz, z},
+ * {P.xyz, hit}, {albedo.rgb, 0}.  Each of the pixel's num_subpixels^2
+ * sub-pixels sends ONE deterministic camera ray -- the renderer's camera ray
+ * with both jitter draws 0.5 and no lens offset -- through the renderer's own
+ * nearest-hit scan in its exact arithmetic.  Per hitting ray: the facing
+ * normal n, the point P = o + t d, the distance z = t |d| and the sphere's
+ * colour; hit is the fraction of the rays that hit a sphere, the others are
+ * means over the hitting rays (n is not re-normalised), 0 when none hits
+ * except the albedo, which is (1, 1, 1) for the sky.  No RNG: the result does
+ * not depend on seed, samples or flags.  d_feat must be 16-byte aligned
+ * (PTG_ERR_INVALID_ARGUMENT otherwise).  Asynchronous on stream. */
+int ptg_features_device(ptg_context *ctx, const ptg_params *params, float *d_feat, void *stream);
+
+typedef struct ptg_denoise_params {
+    int32_t iterations;  /* 0..8 (0 copies the input); iteration i has step 1 << i */
+    int32_t reserved0_;
+    float k_color;       /* weight of |c_p - c_q|^2 / (Vbar_p + Vbar_q + eps_color) */
+    float k_normal;      /* weight of max(0, 1 - n_p.n_q), and of |hit_p - hit_q| */
+    float k_plane;       /* weight of |n_p.(P_q - P_p)| / (step pixel_spread max(z_p, 1e-4)) */
+    float k_albedo;      /* weight of |a_p - a_q|^2 */
+    float eps_color;     /* > 0 */
+    float pixel_spread;  /* world size of a pixel at distance 1 (ptg_pixel_spread); > 0 */
+    float reserved_[8];
+} ptg_denoise_params;
+
+/* The defaults (host only).  pixel_spread is 1/1024, a 53 degree field of
+ * view 1024 pixels across: callers with a camera set it from ptg_pixel_spread. */
+int ptg_denoise_defaults(ptg_denoise_params *out);
+/* Host only: max(|X| / width, |Y| / height) / |base + X/2 + Y/2| of the
+ * camera's image plane (X, Y its axes, base its lower left corner less the
+ * position): what one pixel spans at distance 1 along the central ray. */
+int ptg_pixel_spread(const ptg_camera *cam, int32_t width, int32_t height, float *spread);
+/* Host only: the scratch ptg_denoise_device needs for a width x height frame. */
+int ptg_denoise_scratch_bytes(int32_t width, int32_t height, size_t *bytes);
+
+/* The filter, all fp32 in a fixed operation order with explicit fmaf and
+ * correctly rounded division (csrc/denoise_filter.hpp), so ptg_denoise_host
+ * reproduces every bit on a CPU.  Whole frames with row stride width (a
+ * shard_count = 1 slab, or a gathered frame): d_color, d_var, d_out, d_var_out
+ * (optional) width * height * 3 floats, d_feat width * height * 12.  The
+ * outputs must not overlap the inputs.
+ *   before iteration i: Vbar_p = the 3x3 [1 2 1]x[1 2 1]/16 average of
+ *     V_r + V_g + V_b, coordinates clamped to the image, of the input
+ *     variance (i = 0) or of the previous iteration's output variance
+ *   iteration i, s = 1 << i, taps q = p + s (dx, dy), dx, dy in -2..2, inside
+ *   the image, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+ *     x = k_color |c_p - c_q|^2 / (Vbar_p + Vbar_q + eps_color)
+ *       + k_normal max(0, 1 - n_p.n_q)
+ *       + k_plane |n_p.(P_q - P_p)| / (s pixel_spread max(z_p, 1e-4))
+ *       + k_albedo |a_p - a_q|^2
+ *       + (hit_p == hit_q ? 0 : k_normal |hit_p - hit_q|)
+ *     with hit_p = 0 or hit_q = 0 (sky): the colour term alone when both are
+ *     0, else the tap is skipped
+ *     t = max(0, 1 - x / 8), w = h(dx) h(dy) t^8 (three squarings): a tap
+ *     with x >= 8 contributes exactly 0
+ *     c'_p = sum w c_q / sum w, V'_p = sum w^2 V_q / (sum w)^2 per channel
+ *     (the centre tap is taken at x = 0 -- a mean normal may be shorter
+ *     than 1 -- so sum w >= 9/64)
+ *   after the last iteration d_out = c', d_var_out = V'.
+ * Asynchronous on stream, no allocation inside: d_scratch of at least
+ * ptg_denoise_scratch_bytes.  PTG_ERR_INVALID_ARGUMENT for a NULL buffer,
+ * iterations outside 0..8, eps_color or pixel_spread <= 0, a negative or
+ * non-finite k, or too small a scratch. */
+int ptg_denoise_device(const float *d_color, const float *d_var, const float *d_feat, int32_t width, int32_t height,
+                       const ptg_denoise_params *params, float *d_out, float *d_var_out, void *d_scratch,
+                       size_t scratch_bytes, void *stream);
+/* The same arithmetic as a host loop over host buffers (no device, no
+ * scratch): the filter's CPU statement, what the tests compare the kernels
+ * with.  Synchronous. */
+int ptg_denoise_host(const float *color, const float *var, const float *feat, int32_t width, int32_t height,
+                     const ptg_denoise_params *params, float *out, float *var_out);
+
+/* Render and denoise.  Synchronous; params->shard_count must be 1 and
+ * params->samples >= 2.  Reset, ONE PTG_FLAG_MOMENTS pass over
+ * [0, samples), resolve, ptg_noise_device for the variance slab,
+ * ptg_features_device, ptg_denoise_device; then ADDS into image_rgb in
+ * ptg_render's row order.  denoise NULL: the defaults with the camera's
+ * pixel_spread (also taken from the camera when the given one is 0).
+ * PTG_FLAG_EXACT_MATH and PTG_FLAG_LIGHT_SAMPLING are honoured;
+ * PTG_FLAG_REFERENCE_F64 is PTG_ERR_UNSUPPORTED.  With iterations = 0 the
+ * image equals ptg_render's at the same samples bit for bit. */
+int ptg_render_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                        const ptg_params *params, int device, const ptg_denoise_params *denoise,
+                        double *image_rgb);
+/* ptg_render_to_noise, then the filter on the frame it stopped at: the same
+ * schedule, checks, stop rule and report; the passes carry the moments
+ * anyway, so nothing is rendered twice.  The image equals
+ * ptg_render_denoised's at samples = report->samples_done bit for bit.
+ * samples >= 2; report optional. */
+int ptg_render_to_noise_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                                 const ptg_params *params, int device, const ptg_noise_target *target,
+                                 const ptg_denoise_params *denoise, double *image_rgb, ptg_noise_report *report);
+/* Host helper: ptg_features_device's frame copied to the host, width *
+ * height * 12 floats in ptg_render's row order (row r is the reference's
+ * y = height - 1 - r).  Synchronous; params->shard_count must be 1. */
+int ptg_features(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
+                 int device, float *features);
+
 /* Reassemble shard_count gathered slabs (rank-major, as all-gather lays them
  * out) into the width*height*3 image. */
 int ptg_unshard_device(const float *d_gathered, float *d_image, int32_t width, int32_t height,
