@@ -1174,9 +1174,11 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
     // main.cpp:126
     if constexpr (kLS) {
         // the hit after a light-sampling step: the listed emitters were
-        // sampled there (their ids by wave-uniform loads)
+        // sampled there (their ids by wave-uniform loads) -- those met on
+        // their front face.  A back face means the previous hit point lay
+        // inside that light, where the step adds nothing: it counts here
         bool listed = false;
-        if (io.skip)
+        if (io.skip & front)
             for (int k = 0; k < io.n_lights; ++k)
                 listed |= io.hid == __float_as_int(io.lights[k].e.w);
         if (!listed)
@@ -1398,7 +1400,9 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
             const float4 lc = lr->c, le = lr->e;
             const f3 w = mk3(lc.x - p.x, lc.y - p.y, lc.z - p.z);
             const float d2 = dot3(w, w);
-            // (a point inside the light, d2 <= R^2, cannot occur in a valid scene: nothing)
+            // (a point inside the light, d2 <= R^2 -- a dome light, a lamp of
+            // emissive glass: nothing here; the next hit can only meet that
+            // light from the back, where its emission is not skipped)
             if (d2 > lc.w && io.hid != __float_as_int(le.w)) {
                 const float q = Math<kExact>::div(lc.w, d2);
                 const float omc = Math<kExact>::div(q, 1.0f + Math<kExact>::sqrt0(1.0f - q));  // 1 - cos theta_max

@@ -18,6 +18,8 @@
 // oracle's Mode A/xs (oracle/pt_oracle.c, the same restatement on the CPU) is
 // its exact counterpart: IEEE division and square root are correctly rounded
 // on both sides, and only sin/cos/pow may differ from glibc's in the last ulp.
+// With a light list the sin and cos are sincos_plain's on both sides, the same
+// bits, and only pow is left.
 //
 // One lane per sub-pixel, its samples in order (the reference's loop);
 // 16 pixels x 4 sub-pixels per wave; a pixel's 4 lanes combine their clamped
@@ -119,6 +121,41 @@ __device__ inline void specular(const Hit &h, d3 d, uint32_t &st, d3 &ro, d3 &rd
     rd = add(refl, mk(f, f, f));
 }
 
+// The light-sampling estimator's sin and cos (include/ptgpu.h), a in
+// [0, 2 pi]: plain double operations only (the build fuses nothing), so the
+// CPU oracle computes the same bits -- the step puts a cosine of the sampled
+// geometry into a path's value, where a math library's last bit would show.
+// Reduction by the nearest multiple of pi/2 in three pieces (the first two of
+// 33 bits: k * piece is exact), then the fdlibm kernels k_sin.c / k_cos.c
+// (Copyright (C) 1993 by Sun Microsystems, Inc.; permission to use, copy,
+// modify and distribute is freely granted provided this notice is preserved)
+// on the head x and tail y.
+__device__ inline void sincos_plain(double a, double &sn, double &cs)
+{
+    const double k = floor(a * 6.36619772367581382433e-01 + 0.5);
+    double r = a - k * 1.57079632673412561417e+00;
+    double w = k * 6.07710050630396597660e-11;
+    const double t = r;
+    r = t - w;
+    w = k * 2.02226624879595063154e-21 - ((t - r) - w);
+    const double x = r - w, y = (r - x) - w;  // a - k pi/2 = x + y
+    const double z = x * x, v = z * x;
+    const double ps =
+        8.33333333332248946124e-03 +
+        z * (-1.98412698298579493134e-04 +
+             z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10)));
+    const double s = x - ((z * (0.5 * y - v * ps) - y) - v * -1.66666666666666324348e-01);
+    const double z2 = z * z;
+    const double pc =
+        z * (4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * 2.48015872894767294178e-05)) +
+        (z2 * z2) * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11));
+    const double hz = 0.5 * z, o = 1.0 - hz;
+    const double c = o + (((1.0 - o) - hz) + (z * pc - x * y));
+    const int quad = (int)k & 3;
+    sn = quad == 0 ? s : quad == 1 ? c : quad == 2 ? -s : -c;
+    cs = quad == 0 ? c : quad == 1 ? -s : quad == 2 ? -c : s;
+}
+
 // main.cpp:104-158 for the path starting at (o, d); segs += scene scans.
 // n_lights > 0 (PTG_FLAG_LIGHT_SAMPLING, include/ptgpu.h): the light-sampling
 // step at every diffuse hit that continues the path, with the fp32 kernels'
@@ -128,7 +165,7 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
                               int n_lights = 0)
 {
     d3 E = mk(0, 0, 0), T = mk(1, 1, 1);
-    bool skip = false;  // this hit follows a light-sampling step: the listed emitters' emission is not added
+    bool skip = false;  // this hit follows a light-sampling step: a listed emitter's front face adds no emission
     for (int depth = 0; depth < kDepthLimit; ++depth) {
         double t = 0.0;
         segs += 1;
@@ -142,8 +179,11 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
         const ptg_sphere &obj = s[id];
         const Hit h = hit_record(obj, o, d, t);
         d3 color = ld(obj.color);
+        // a listed emitter met on its front face was sampled at the previous
+        // hit; one met from inside (back face) was not: step 3 adds nothing
+        // for a light the hit point lies in, so its emission counts here
         bool listed = false;
-        for (int k = 0; skip && k < n_lights; ++k)
+        for (int k = 0; skip && h.front && k < n_lights; ++k)
             listed = listed || lights[k] == id;
         skip = false;
         if (!listed)
@@ -178,7 +218,9 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
                     const d3 sw = norm(w);
                     const d3 su = norm(cross(fabs(sw.x) > 0.1 ? mk(0, 1, 0) : mk(1, 0, 0), sw));
                     const d3 sv = cross(sw, su);
-                    const d3 l = add(add(mul(mul(su, cos(ph)), sn), mul(mul(sv, sin(ph)), sn)), mul(sw, ct));
+                    double sph, cph;
+                    sincos_plain(ph, sph, cph);
+                    const d3 l = add(add(mul(mul(su, cph), sn), mul(mul(sv, sph), sn)), mul(sw, ct));
                     const double cs = dot(h.n, l);
                     if (cs > 0) {  // the shadow segment: an ordinary scan from the hit point
                         double ts = 0.0;
@@ -195,7 +237,14 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
             const d3 w = h.n;
             const d3 u = norm(cross(fabs(w.x) > 0.1 ? mk(0, 1, 0) : mk(1, 0, 0), w));
             const d3 v = cross(w, u);
-            d = norm(add(add(mul(mul(u, cos(phi)), sth), mul(mul(v, sin(phi)), sth)), mul(w, cth)));
+            double sphi, cphi;
+            if (n_lights > 0) {  // the estimator's own (no light: the plain mode's bits)
+                sincos_plain(phi, sphi, cphi);
+            } else {  // the reference's libm
+                sphi = sin(phi);
+                cphi = cos(phi);
+            }
+            d = norm(add(add(mul(mul(u, cphi), sth), mul(mul(v, sphi), sth)), mul(w, cth)));
             o = h.p;
         } else if (obj.material == PTG_SPECULAR) {
             specular(h, d, st, o, d);

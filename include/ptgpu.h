@@ -154,10 +154,21 @@ typedef struct ptg_params {
  *        if cs > 0: a shadow segment, an ordinary nearest-hit scan from p
  *        along l (counted like any scan); if its winner is light k:
  *        E += T * Le_k * (cs 2 omc L)
- *   4. the path's next hit skips the emission of the spheres on the light
- *      list (that one hit only; also when step 3 added nothing).  After a
- *      mirror or dielectric bounce and at the camera ray emission counts as
- *      without the flag; huge emitters and the sky always count.
+ *   4. the path's next hit skips the emission of a sphere on the light list
+ *      when it meets that sphere on its FRONT face (that one hit only; also
+ *      when step 3 added nothing).  A listed sphere met from inside (back
+ *      face) counts: p then lies in or on the inside of that sphere (a dome
+ *      light, a lamp of emissive glass), where step 3 adds nothing for it --
+ *      and a point outside a sphere can only meet it from the front.  After
+ *      a mirror or dielectric bounce and at the camera ray emission counts
+ *      as without the flag; huge emitters and the sky always count.
+ * In double (PTG_FLAG_REFERENCE_F64, the oracle) the sin and cos of step 3
+ * and of the BRDF's direction that follows are, with L > 0, computed in plain
+ * double operations (ref64.hpp sincos_plain = the oracle's po_sincos_plain,
+ * within 1 ulp of libm's), not by a math library: cs carries the sampled
+ * geometry into the path's value, so a library's last bit would show in the
+ * image, and the two sides are to agree to the bit.  The fp32 kernels keep
+ * their own table.
  * Both estimators are unbiased for the same integral, so their RAW means
  * agree; the image clamps every sub-pixel mean to [0, 1], and the plain
  * estimator's heavier tails are clipped more often -- clamped images of

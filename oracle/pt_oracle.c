@@ -313,8 +313,55 @@ static recA rec_from(const double rec[10], const double o[3], const double d[3])
     return r;
 }
 
-/* main.cpp:44-58 */
-static void diffuse_A(const recA *rec, rngA *r, v3 *ro, v3 *rd)
+/* sin and cos of a in [0, 2 pi] in plain double operations: no libm, no FMA, no
+ * table, so that every build, the GPU's included, computes the same bits.  The
+ * light-sampling estimator (include/ptgpu.h) is defined with these: its step
+ * puts a cosine of the sampled geometry into the VALUE of a path, where the
+ * last bit of a math library's sin/cos would show in the image.  The argument
+ * is reduced by the nearest multiple of pi/2 held in three pieces (the first
+ * two of 33 bits, so k * piece is exact), then the fdlibm kernels k_sin.c /
+ * k_cos.c (Copyright (C) 1993 by Sun Microsystems, Inc.; permission to use,
+ * copy, modify and distribute is freely granted provided this notice is
+ * preserved) run on the head x and tail y.  Within 1 ulp of the true value
+ * (tests/test_oracle_light_sampling.py); on the 2^24 arguments 2 pi m 2^-24 it
+ * differs from glibc's in 3 % of the results, by one ulp. */
+static void sincos_plain_A(double a, double *sn, double *cs)
+{
+    const double k = floor(a * 6.36619772367581382433e-01 + 0.5);
+    double r = a - k * 1.57079632673412561417e+00;
+    double w = k * 6.07710050630396597660e-11;
+    const double t = r;
+    r = t - w;
+    w = k * 2.02226624879595063154e-21 - ((t - r) - w);
+    const double x = r - w, y = (r - x) - w; /* a - k pi/2 = x + y */
+    const double z = x * x, v = z * x;
+    const double ps =
+        8.33333333332248946124e-03 +
+        z * (-1.98412698298579493134e-04 +
+             z * (2.75573137070700676789e-06 + z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10)));
+    const double s = x - ((z * (0.5 * y - v * ps) - y) - v * -1.66666666666666324348e-01);
+    const double z2 = z * z;
+    const double pc =
+        z * (4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * 2.48015872894767294178e-05)) +
+        (z2 * z2) * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11));
+    const double hz = 0.5 * z, o = 1.0 - hz;
+    const double c = o + (((1.0 - o) - hz) + (z * pc - x * y));
+    switch ((int)k & 3) {
+    case 0: *sn = s, *cs = c; break;
+    case 1: *sn = c, *cs = -s; break;
+    case 2: *sn = -s, *cs = -c; break;
+    default: *sn = -c, *cs = s; break;
+    }
+}
+
+void po_sincos_plain(const double *a, size_t n, double *sn, double *cs)
+{
+    for (size_t i = 0; i < n; ++i)
+        sincos_plain_A(a[i], &sn[i], &cs[i]);
+}
+
+/* main.cpp:44-58; plain_trig: sincos_plain_A instead of libm (light sampling) */
+static void diffuse_A_trig(const recA *rec, rngA *r, v3 *ro, v3 *rd, int plain_trig)
 {
     double phi = 2 * PO_PI * drawA(r);
     double ra = drawA(r);
@@ -323,10 +370,15 @@ static void diffuse_A(const recA *rec, rngA *r, v3 *ro, v3 *rd)
     v3 w = rec->n;
     v3 u = vnorm(vcross(fabs(w.x) > 0.1 ? mk(0, 1, 0) : mk(1, 0, 0), w));
     v3 v = vcross(w, u);
-    v3 nd = vnorm(vadd(vadd(vmul(vmul(u, cos(phi)), st), vmul(vmul(v, sin(phi)), st)), vmul(w, ct)));
+    double sp = sin(phi), cp = cos(phi);
+    if (plain_trig)
+        sincos_plain_A(phi, &sp, &cp);
+    v3 nd = vnorm(vadd(vadd(vmul(vmul(u, cp), st), vmul(vmul(v, sp), st)), vmul(w, ct)));
     *ro = rec->p;
     *rd = nd;
 }
+
+static void diffuse_A(const recA *rec, rngA *r, v3 *ro, v3 *rd) { diffuse_A_trig(rec, r, ro, rd, 0); }
 
 /* main.cpp:60-67 */
 static void specular_A(const recA *rec, rngA *r, v3 *ro, v3 *rd)
@@ -512,6 +564,195 @@ int po_render_xs_f64(const po_sphere *s, int n, const po_camera *cam, int W, int
     if (segments)
         *segments = total;
     return 0;
+}
+
+/* ---- Mode A / xs with a light list (PTG_FLAG_LIGHT_SAMPLING) ------------- */
+/* The estimator include/ptgpu.h defines, written from that text in double
+ * with the helpers above: the draw order per diffuse hit that continues the
+ * path is [roulette] [light] u1 u2 phi r.  lights = scene indices. */
+static int on_list_A(const int32_t *lights, int n_lights, int id)
+{
+    for (int k = 0; k < n_lights; ++k)
+        if (lights[k] == id)
+            return 1;
+    return 0;
+}
+
+/* steps 1-3 at the hit rec of sphere id, throughput T (the hit's colour
+ * included); returns what step 3 adds to E */
+static v3 sample_light_A(const po_sphere *s, int n, const int32_t *lights, int n_lights, int id, const recA *rec, v3 T,
+                         rngA *r, int *segs)
+{
+    int k = 0;
+    if (n_lights > 1) { /* 1. */
+        k = (int)floor(drawA(r) * n_lights);
+        if (k > n_lights - 1)
+            k = n_lights - 1;
+    }
+    double u1 = drawA(r), u2 = drawA(r); /* 2. */
+    const po_sphere *lt = &s[lights[k]];
+    v3 w = vsub(ld3(lt->position), rec->p); /* 3. */
+    double d2 = vdot(w, w), R2 = lt->radius * lt->radius;
+    if (!(d2 > R2) || id == lights[k])
+        return mk(0, 0, 0);
+    double q = R2 / d2;
+    double omc = q / (1.0 + sqrt(1.0 - q));
+    double a = u1 * omc, ct = 1.0 - a, st = sqrt(a * (2.0 - a)), phi = 2 * PO_PI * u2;
+    v3 sw = vnorm(w);
+    v3 su = vnorm(vcross(fabs(sw.x) > 0.1 ? mk(0, 1, 0) : mk(1, 0, 0), sw));
+    v3 sv = vcross(sw, su);
+    double sp, cp;
+    sincos_plain_A(phi, &sp, &cp);
+    v3 l = vadd(vadd(vmul(vmul(su, cp), st), vmul(vmul(sv, sp), st)), vmul(sw, ct));
+    double cs = vdot(rec->n, l);
+    if (!(cs > 0))
+        return mk(0, 0, 0);
+    double t = 0.0;
+    int hit = -1;
+    (*segs)++; /* the shadow segment is a scan like any other */
+    if (!intersect_A(s, n, rec->p, l, &t, &hit) || hit != lights[k])
+        return mk(0, 0, 0);
+    return vmul(vblend(T, ld3(lt->emission)), cs * 2.0 * omc * n_lights);
+}
+
+static v3 radiance_A_ls(const po_sphere *s, int n, v3 o, v3 d, rngA *r, int *segs, const int32_t *lights,
+                        int n_lights)
+{
+    v3 E = mk(0, 0, 0), T = mk(1, 1, 1);
+    int sampled = 0; /* the previous hit ran the light-sampling step */
+    *segs = 0;
+    for (int depth = 0; depth < PO_DEPTH_LIMIT; ++depth) {
+        double t = 0.0;
+        int id = 0;
+        (*segs)++;
+        if (!intersect_A(s, n, o, d, &t, &id)) {
+            v3 ud = vnorm(d);
+            double tt = 0.5 * (ud.y + 1.0);
+            v3 bg = vadd(vmul(mk(1, 1, 1), 1.0 - tt), vmul(mk(0.5, 0.7, 1.0), tt));
+            return vadd(E, vblend(T, bg));
+        }
+        const po_sphere *obj = &s[id];
+        recA rec = hit_record_A(obj, o, d, t);
+        v3 color = ld3(obj->color);
+        /* 4. a listed emitter met on its front face was sampled at the
+         * previous hit; from inside (back face) step 3 added nothing for it */
+        if (!(sampled && rec.front && on_list_A(lights, n_lights, id)))
+            E = vadd(E, vblend(T, ld3(obj->emission)));
+        sampled = 0;
+        double p = color.x;
+        if (p < color.y) p = color.y;
+        if (p < color.z) p = color.z;
+        if (depth > PO_RR_THRESHOLD) {
+            if (drawA(r) < p)
+                color = vmul(color, 1.0 / p);
+            else
+                return E;
+        }
+        T = vblend(T, color);
+        switch (obj->material) {
+        case 0:
+            if (n_lights > 0 && depth + 1 < PO_DEPTH_LIMIT) { /* the path goes on */
+                E = vadd(E, sample_light_A(s, n, lights, n_lights, id, &rec, T, r, segs));
+                sampled = 1;
+            }
+            diffuse_A_trig(&rec, r, &o, &d, n_lights > 0); /* no light: the plain mode's bits */
+            break;
+        case 1: specular_A(&rec, r, &o, &d); break;
+        default: dielectric_A(&rec, r, &o, &d); break;
+        }
+    }
+    return E;
+}
+
+static int check_lights(int n, const int32_t *lights, int n_lights)
+{
+    if (n_lights < 0 || (n_lights > 0 && !lights))
+        return 1;
+    for (int k = 0; k < n_lights; ++k)
+        if (lights[k] < 0 || lights[k] >= n)
+            return 1;
+    return 0;
+}
+
+/* one path of sub-pixel (x, y, sx, sy): main.cpp:186-191 */
+static v3 path_A_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int nsub, int x, int y, int sx,
+                    int sy, uint64_t key, uint32_t sample, const int32_t *lights, int n_lights, int *sg)
+{
+    rngA r = {NULL, po_sample_state(key, sample), 0};
+    double sl = 1.0 / nsub;
+    double xin = (x + sx * sl + drawA_between(&r, 0.0, sl));
+    double yin = (y + sy * sl + drawA_between(&r, 0.0, sl));
+    v3 o, d;
+    cam_get_ray_A(cam, xin / W, yin / H, &r, &o, &d);
+    return radiance_A_ls(s, n, o, d, &r, sg, lights, n_lights);
+}
+
+static uint64_t sub_key(uint64_t seed, int W, int nsub, int x, int y, int sx, int sy)
+{
+    return po_key_hash(seed, ((uint64_t)y * (uint64_t)W + (uint64_t)x) * (uint64_t)(nsub * nsub) +
+                                 (uint64_t)(sy * nsub + sx));
+}
+
+static int render_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,
+                     uint64_t seed, const int32_t *lights, int n_lights, int y0, int y1, int ystep, int nthreads,
+                     int raw, double *image, uint64_t *segments)
+{
+    if (check_args(n, W, H, samps, nsub) || ystep <= 0 || check_lights(n, lights, n_lights))
+        return -1;
+    uint64_t total = 0;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1) reduction(+ : total)
+    for (int y = y0; y < y1; y += ystep) {
+        for (int x = 0; x < W; ++x)
+            for (int sy = 0; sy < nsub; ++sy)
+                for (int sx = 0; sx < nsub; ++sx) {
+                    uint64_t key = sub_key(seed, W, nsub, x, y, sx, sy);
+                    v3 a = mk(0, 0, 0);
+                    for (int k = 0; k < samps; ++k) {
+                        int sg = 0;
+                        v3 c = path_A_ls(s, n, cam, W, H, nsub, x, y, sx, sy, key, (uint32_t)k, lights, n_lights,
+                                         &sg);
+                        total += (uint64_t)sg;
+                        a = vadd(a, vmul(c, 1.0 / samps));
+                    }
+                    double *px = image + 3 * ((size_t)(H - y - 1) * (size_t)W + (size_t)x);
+                    double q = 1.0 / (nsub * nsub);
+                    px[0] = px[0] + (raw ? a.x : po_clamp(a.x)) * q;
+                    px[1] = px[1] + (raw ? a.y : po_clamp(a.y)) * q;
+                    px[2] = px[2] + (raw ? a.z : po_clamp(a.z)) * q;
+                }
+    }
+    if (segments)
+        *segments = total;
+    return 0;
+}
+
+int po_render_xs_f64_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,
+                        uint64_t seed, const int32_t *lights, int n_lights, int y0, int y1, int ystep, int nthreads,
+                        double *image, uint64_t *segments)
+{
+    return render_ls(s, n, cam, W, H, samps, nsub, seed, lights, n_lights, y0, y1, ystep, nthreads, 0, image,
+                     segments);
+}
+
+int po_raw_means_xs_f64_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,
+                           uint64_t seed, const int32_t *lights, int n_lights, int y0, int y1, int ystep,
+                           int nthreads, double *means, uint64_t *segments)
+{
+    return render_ls(s, n, cam, W, H, samps, nsub, seed, lights, n_lights, y0, y1, ystep, nthreads, 1, means,
+                     segments);
+}
+
+int po_sample_xs_f64_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int nsub, uint64_t seed,
+                        int x, int y, int sx, int sy, uint32_t sample, const int32_t *lights, int n_lights,
+                        double out[3])
+{
+    if (check_args(n, W, H, 1, nsub) || check_lights(n, lights, n_lights))
+        return -1;
+    int sg = 0;
+    v3 c = path_A_ls(s, n, cam, W, H, nsub, x, y, sx, sy, sub_key(seed, W, nsub, x, y, sx, sy), sample, lights,
+                     n_lights, &sg);
+    st3(out, c);
+    return sg;
 }
 
 /* ========================================================================= */

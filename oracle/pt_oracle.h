@@ -137,6 +137,30 @@ uint32_t po_xorshift32(uint32_t *state);
 int po_render_xs_f64(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,
                      uint64_t seed, int y0, int y1, int ystep, int nthreads, double *image,
                      uint64_t *segments);
+/* Mode A / xs with PTG_FLAG_LIGHT_SAMPLING's estimator (include/ptgpu.h),
+ * written from that text in double: lights = the light list as scene indices
+ * (ptg_light_list), n_lights of them, each in [0, n).  The draws of a diffuse
+ * hit that continues the path come in the order [roulette] [light] u1 u2 phi r;
+ * shadow segments count as segments.  With n_lights = 0 the image and the
+ * count equal po_render_xs_f64's bit for bit. */
+int po_render_xs_f64_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,
+                        uint64_t seed, const int32_t *lights, int n_lights, int y0, int y1, int ystep, int nthreads,
+                        double *image, uint64_t *segments);
+/* ... the raw means: per pixel and channel sum_sub (sum_k c_k / samps) / nsub^2
+ * with the same summation order and NO clamp of the sub-pixel means -- what
+ * estimators are compared on (DESIGN.md "Light sampling", the clamp trap).
+ * means: W*H*3 doubles, reference row order, accumulated into. */
+int po_raw_means_xs_f64_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,
+                           uint64_t seed, const int32_t *lights, int n_lights, int y0, int y1, int ystep,
+                           int nthreads, double *means, uint64_t *segments);
+/* ... one path: the radiance of sample `sample` of sub-pixel (sx, sy) of pixel
+ * (x, y) (y from the bottom, main.cpp:181); returns its segment count, or -1. */
+int po_sample_xs_f64_ls(const po_sphere *s, int n, const po_camera *cam, int W, int H, int nsub, uint64_t seed,
+                        int x, int y, int sx, int sy, uint32_t sample, const int32_t *lights, int n_lights,
+                        double out[3]);
+/* The light-sampling estimator's sin and cos (include/ptgpu.h) of n angles in
+ * [0, 2 pi]: plain double operations only, the same bits on every build. */
+void po_sincos_plain(const double *a, size_t n, double *sn, double *cs);
 /* Mode B / xs: float arithmetic (GPU op sequence).  image: W*H*3 floats,
  * reference row order, overwritten for the rows rendered. */
 int po_render_xs_f32(const po_sphere *s, int n, const po_camera *cam, int W, int H, int samps, int nsub,

@@ -74,6 +74,10 @@ def lib():
             "po_render_xs_f64_rect": (I, [P, I, P, I, I, I, I, U64, I, I, I, I, I, I, P, P]),
             "po_render_xs_f32_rect": (I, [P, I, P, I, I, I, I, U64, I, I, I, I, I, I, P, P]),
             "po_sample_f32": (I, [P, I, P, I, I, I, U64, I, I, I, I, U32, P]),
+            "po_render_xs_f64_ls": (I, [P, I, P, I, I, I, I, U64, P, I, I, I, I, I, P, P]),
+            "po_raw_means_xs_f64_ls": (I, [P, I, P, I, I, I, I, U64, P, I, I, I, I, I, P, P]),
+            "po_sample_xs_f64_ls": (I, [P, I, P, I, I, I, U64, I, I, I, I, U32, P, I, P]),
+            "po_sincos_plain": (None, [P, C.c_size_t, P, P]),
             "po_tonemap": (None, [P, C.c_size_t, P]),
             "po_scan_layout": (I, [P, I, P, P, P]),
             "po_sincos2pi": (None, [P, C.c_size_t, P]),
@@ -177,6 +181,43 @@ def render_xs_f64(spheres, cam, W, H, samps, nsub=2, seed=0x5EED0001, rows=None,
                                 y0, y1, ys, nthreads, ptr(img), ptr(segs))
     assert rc == 0
     return img.reshape(H, W, 3), int(segs[0])
+
+
+def _lights(lights) -> np.ndarray:
+    """The light list (scene indices, as ptgpu.light_list gives them) as int32; never empty storage."""
+    a = np.ascontiguousarray(np.asarray(list(lights), dtype=np.int32).reshape(-1))
+    return a if a.size else np.zeros(1, dtype=np.int32)
+
+
+def render_xs_f64_ls(spheres, cam, W, H, samps, lights, nsub=2, seed=0x5EED0001, rows=None, nthreads=8, raw=False):
+    """Mode A/xs with PTG_FLAG_LIGHT_SAMPLING's estimator over the light list
+    `lights` (scene indices): the image (raw=False, clamped sub-pixel means) or
+    the raw per-pixel-channel means (raw=True), and the segment count."""
+    y0, y1, ys = rows if rows is not None else (0, H, 1)
+    img = np.zeros((H * W * 3,), dtype=np.float64)
+    segs = np.zeros(1, dtype=np.uint64)
+    fn = lib().po_raw_means_xs_f64_ls if raw else lib().po_render_xs_f64_ls
+    rc = fn(ptr(spheres), len(spheres), ptr(cam), W, H, samps, nsub, seed, ptr(_lights(lights)), len(lights),
+            y0, y1, ys, nthreads, ptr(img), ptr(segs))
+    assert rc == 0
+    return img.reshape(H, W, 3), int(segs[0])
+
+
+def sample_xs_f64_ls(spheres, cam, W, H, nsub, seed, x, y, sx, sy, sample, lights):
+    """One Mode A/xs path with the light list: its radiance (3 doubles) and segment count."""
+    out = np.zeros(3)
+    segs = lib().po_sample_xs_f64_ls(ptr(spheres), len(spheres), ptr(cam), W, H, nsub, seed, x, y, sx, sy, sample,
+                                     ptr(_lights(lights)), len(lights), ptr(out))
+    assert segs >= 0
+    return out, segs
+
+
+def sincos_plain(a):
+    """The light-sampling estimator's (sin a, cos a) of the angles a in [0, 2 pi]."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    s, c = np.empty_like(a), np.empty_like(a)
+    lib().po_sincos_plain(ptr(a), a.size, ptr(s), ptr(c))
+    return s, c
 
 
 def render_xs_f32(spheres, cam, W, H, samps, nsub=2, seed=0x5EED0001, rows=None, nthreads=8):
