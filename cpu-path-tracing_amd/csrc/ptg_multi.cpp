@@ -33,6 +33,10 @@
 // ptg_last_error is thread-local in ptg_render.hip; errors raised here go
 // through the same channel
 extern "C" int ptg_set_error_(int code, const char *msg);
+// csrc/ptg_denoise.hip: the filter parameters a driver runs with (NULL: the
+// defaults; the camera's pixel_spread where none is given), checked
+extern "C" int ptg_denoise_params_for_(const ptg_camera *cam, int32_t width, int32_t height,
+                                       const ptg_denoise_params *denoise, ptg_denoise_params *out);
 
 namespace {
 
@@ -46,6 +50,8 @@ struct Shard {
     hipEvent_t t_begin = nullptr, t_rendered = nullptr;  // timing of the last device frame
     float *slab = nullptr;
     size_t slab_cap = 0;  // floats
+    float *var = nullptr;  // denoised frames: the variance slab, laid out like the slab
+    size_t var_cap = 0;
     unsigned long long *counters = nullptr;  // PTG_FLAG_COUNT_TESTS: 4 per shard
     ncclComm_t comm = nullptr;
     bool stuck = false;  // destroy(): a broken group's stream did not drain
@@ -115,6 +121,15 @@ struct ptg_multi {
     unsigned long long *host_stats = nullptr;
     std::vector<uint8_t> host_mask;
     std::vector<int32_t> host_cnt;
+    // denoised frames (reserve_denoise): the camera (the filter's pixel_spread)
+    // and ONE allocation on the root, sized on first use: the gathered
+    // variance slabs, the un-sharded variance, the filtered frame, the whole
+    // frame's features and the filter's scratch
+    ptg_camera cam{};
+    float *dn_buf = nullptr;
+    size_t dn_cap = 0;  // floats
+    float *var_gathered = nullptr, *var_image = nullptr, *filtered = nullptr, *feat = nullptr, *dn_scratch = nullptr;
+    size_t dn_scratch_bytes = 0;
 };
 
 namespace {
@@ -165,6 +180,8 @@ int destroy(ptg_multi *m)
         }
         if (s.slab)
             (void)hipFree(s.slab);
+        if (s.var)
+            (void)hipFree(s.var);
         if (s.counters)
             (void)hipFree(s.counters);
         for (void *q : {(void *)s.over, (void *)s.over_all, (void *)s.stats, (void *)s.cnt})
@@ -187,6 +204,8 @@ int destroy(ptg_multi *m)
             (void)hipFree(m->gathered);
         if (m->image)
             (void)hipFree(m->image);
+        if (m->dn_buf)
+            (void)hipFree(m->dn_buf);
         if (m->t_unsharded)
             (void)hipEventDestroy(m->t_unsharded);
     }
@@ -217,6 +236,8 @@ int create(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, c
     DeviceGuard g;
     ptg_multi *m = new ptg_multi();
     m->rccl = rccl;
+    if (cam)
+        m->cam = *cam;
     m->shards.resize(n);
     int rc = PTG_OK;
     for (int k = 0; k < n && rc == PTG_OK; ++k) {
@@ -382,16 +403,21 @@ int rccl_group(ptg_multi *m, const char *what, Call &&call)
 // ONE gather of the equal-size slabs to the root (RCCL: one ncclGather per
 // rank inside a group, rank-major on the root -- rccl.h:745; local shards: the
 // same layout by device copies after each shard's slab is complete) and the
-// un-shard there, queued on the root's stream (asynchronous).
-int gather_unshard_device(ptg_multi *m, const ptg_params *p, size_t slab_elems)
+// un-shard there, queued on the root's stream (asynchronous).  variance: the
+// shards' variance slabs into the root's variance frame instead (denoised
+// frames: the same layout, the same path).
+int gather_unshard_device(ptg_multi *m, const ptg_params *p, size_t slab_elems, bool variance = false)
 {
     const int n = (int)m->shards.size();
     Shard &root = m->shards[0];
+    float *const gathered = variance ? m->var_gathered : m->gathered;
+    float *const image = variance ? m->var_image : m->image;
     if (m->rccl) {
         const int rc = rccl_group(m, "ncclGather", [&](int k, Shard &s) {
             return k == m->inject_gather_fault
                        ? ncclInvalidArgument
-                       : ncclGather(s.slab, k == 0 ? m->gathered : nullptr, slab_elems, ncclFloat, 0, s.comm, s.stream);
+                       : ncclGather(variance ? s.var : s.slab, k == 0 ? gathered : nullptr, slab_elems, ncclFloat, 0,
+                                    s.comm, s.stream);
         });
         if (rc)
             return rc;
@@ -402,11 +428,11 @@ int gather_unshard_device(ptg_multi *m, const ptg_params *p, size_t slab_elems)
             Shard &s = m->shards[k];
             MULTI_HIP(hipEventRecord(s.done, s.stream));
             MULTI_HIP(hipStreamWaitEvent(root.stream, s.done, 0));
-            MULTI_HIP(hipMemcpyAsync(m->gathered + (size_t)k * slab_elems, s.slab, slab_elems * sizeof(float),
-                                     hipMemcpyDeviceToDevice, root.stream));
+            MULTI_HIP(hipMemcpyAsync(gathered + (size_t)k * slab_elems, variance ? s.var : s.slab,
+                                     slab_elems * sizeof(float), hipMemcpyDeviceToDevice, root.stream));
         }
     }
-    return ptg_unshard_device(m->gathered, m->image, p->width, p->height, p->band_rows, n, root.stream);
+    return ptg_unshard_device(gathered, image, p->width, p->height, p->band_rows, n, root.stream);
 }
 
 // waits for every shard's stream (root last: its part ends with the un-shard)
@@ -679,6 +705,111 @@ int multi_read_counts(ptg_multi *m, const ptg_params *p, int32_t *counts)
     return PTG_OK;
 }
 
+// ---- denoised frames (include/ptgpu.h "denoising on several GPUs") ----
+// Every input of the filter is bit-identical across shardings -- the colour
+// and the variance come from exact sums, the features depend on the scene, the
+// camera and the global pixel only -- and the filter is a fixed fp32 sequence
+// run once, on the root, over the un-sharded frames: the filtered image equals
+// the one-device driver's bit for bit.
+
+// every shard's variance slab and the root's frames for a frame of this size
+// (after reserve(); grown, never shrunk; freed in destroy())
+int reserve_denoise(ptg_multi *m, const ptg_params *p, size_t slab_elems)
+{
+    const int n = (int)m->shards.size();
+    for (Shard &s : m->shards) {
+        if (s.var_cap >= slab_elems)
+            continue;
+        MULTI_HIP(hipSetDevice(s.id));
+        if (s.var) {
+            MULTI_HIP(hipStreamSynchronize(s.stream));
+            MULTI_HIP(hipFree(s.var));
+            s.var = nullptr;
+            s.var_cap = 0;
+        }
+        if (hipMalloc(&s.var, slab_elems * sizeof(float)) != hipSuccess)
+            return fail(PTG_ERR_OUT_OF_MEMORY, "multi: hipMalloc of a variance slab failed");
+        s.var_cap = slab_elems;
+    }
+    int32_t frame_rows = 0;  // of the whole frame as ONE shard: what the root's ptg_features_device call addresses
+    size_t scratch_bytes = 0;
+    int rc;
+    if ((rc = ptg_shard_rows(p->height, p->band_rows, 1, &frame_rows)) ||
+        (rc = ptg_denoise_scratch_bytes(p->width, p->height, &scratch_bytes)))
+        return rc;
+    // every part starts at a multiple of 64 floats (256 B: ptg_features_device stores float4)
+    const auto part = [](size_t floats) { return (floats + 63) / 64 * 64; };
+    const size_t gath = part((size_t)n * slab_elems), img = part((size_t)p->width * p->height * 3);
+    const size_t feat = part((size_t)frame_rows * p->width * 12), scratch = part(scratch_bytes / sizeof(float));
+    const size_t total = gath + 2 * img + feat + scratch;
+    Shard &r = m->shards[0];
+    MULTI_HIP(hipSetDevice(r.id));
+    if (m->dn_cap < total) {
+        MULTI_HIP(hipStreamSynchronize(r.stream));
+        if (m->dn_buf)
+            MULTI_HIP(hipFree(m->dn_buf));
+        m->dn_buf = nullptr;
+        m->dn_cap = 0;
+        if (hipMalloc(&m->dn_buf, total * sizeof(float)) != hipSuccess)
+            return fail(PTG_ERR_OUT_OF_MEMORY, "multi: hipMalloc of the denoiser's frames failed");
+        m->dn_cap = total;
+    }
+    m->var_gathered = m->dn_buf;
+    m->var_image = m->var_gathered + gath;
+    m->filtered = m->var_image + img;
+    m->feat = m->filtered + img;
+    m->dn_scratch = m->feat + feat;
+    m->dn_scratch_bytes = scratch * sizeof(float);
+    return PTG_OK;
+}
+
+// The sums the shards hold, resolved, filtered and copied to m->host: every
+// shard resolves its slab and writes its variance slab (samples_done > 0:
+// ptg_resolve_device / ptg_noise_device at that count; 0: the *_active pair,
+// each pixel's own count), two gathers through the one helper, two un-shards,
+// the whole frame's features from the root's own context (shard_count 1: they
+// depend on the scene, the camera and the global pixel only, so nothing moves;
+// ptg_features_device plans with_acc = false and touches neither the sums, the
+// counts nor the active list of the root's shard), ONE filter on the root's
+// stream.  Synchronous.
+int multi_resolve_filtered(ptg_multi *m, const ptg_params *p, int32_t samples_done, const ptg_denoise_params &k)
+{
+    size_t slab_elems = 0;
+    int rc;
+    if ((rc = reserve(m, p, slab_elems)) || (rc = reserve_denoise(m, p, slab_elems)))
+        return rc;
+    const int n = (int)m->shards.size();
+    for (int i = 0; i < n; ++i) {
+        Shard &s = m->shards[i];
+        const ptg_params q = shard_params(p, i, n);
+        if (samples_done > 0)
+            rc = ptg_resolve_device(s.ctx, &q, samples_done, s.slab, s.stream);
+        else
+            rc = ptg_resolve_active_device(s.ctx, &q, s.slab, s.stream);
+        if (rc)
+            return rc;
+        if (samples_done > 0)
+            rc = ptg_noise_device(s.ctx, &q, samples_done, 0.0, 1.0, s.var, nullptr, nullptr, s.stream);
+        else
+            rc = ptg_noise_active_device(s.ctx, &q, 1.0, s.var, nullptr, s.stream);
+        if (rc)
+            return rc;
+    }
+    if ((rc = gather_unshard_device(m, p, slab_elems)) || (rc = gather_unshard_device(m, p, slab_elems, /*variance=*/true)))
+        return rc;
+    Shard &root = m->shards[0];
+    if ((rc = ptg_features_device(root.ctx, p, m->feat, root.stream)))  // p: shard_count 1 (check_frame_params)
+        return rc;
+    MULTI_HIP(hipSetDevice(root.id));
+    if ((rc = ptg_denoise_device(m->image, m->var_image, m->feat, p->width, p->height, &k, m->filtered, nullptr,
+                                 m->dn_scratch, m->dn_scratch_bytes, root.stream)))
+        return rc;
+    const size_t image_elems = (size_t)p->width * p->height * 3;
+    MULTI_HIP(hipMemcpyAsync(m->host.data(), m->filtered, image_elems * sizeof(float), hipMemcpyDeviceToHost,
+                             root.stream));
+    return sync_all(m);
+}
+
 double rho_of_bits(unsigned long long bits)
 {
     const uint32_t b = (uint32_t)bits;
@@ -888,8 +1019,11 @@ int ptg_multi_read_sample_counts(ptg_multi *m, const ptg_params *params, int32_t
     return multi_read_counts(m, params, counts);
 }
 
-int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
-                              double *image_rgb, ptg_noise_report *report)
+// ptg_multi_render_to_noise, and with `denoise` ptg_multi_render_to_noise_denoised: the same passes, checks and
+// report, the frame it stopped at through the filter
+static int render_to_noise_on(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
+                              const ptg_denoise_params *denoise, bool filter, double *image_rgb,
+                              ptg_noise_report *report)
 {
     if (!image_rgb || !target)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_to_noise: NULL image or target");
@@ -897,6 +1031,9 @@ int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_
     int rc = check_frame(m, params);
     if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
                                  "multi_render_to_noise", ends, &n_ends)))
+        return rc;
+    ptg_denoise_params dk{};
+    if (filter && (rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &dk)))
         return rc;
     m->timed = false;
     DeviceGuard g;
@@ -925,17 +1062,22 @@ int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_
         if (rep.converged)
             break;
     }
-    size_t slab_elems = 0;
-    if ((rc = reserve(m, &p, slab_elems)))
-        return rc;
-    const int n = (int)m->shards.size();
-    for (int k = 0; k < n; ++k) {
-        const ptg_params q = shard_params(&p, k, n);
-        if ((rc = ptg_resolve_device(m->shards[k].ctx, &q, done, m->shards[k].slab, m->shards[k].stream)))
+    if (filter) {
+        if ((rc = multi_resolve_filtered(m, &p, done, dk)))
+            return rc;
+    } else {
+        size_t slab_elems = 0;
+        if ((rc = reserve(m, &p, slab_elems)))
+            return rc;
+        const int n = (int)m->shards.size();
+        for (int k = 0; k < n; ++k) {
+            const ptg_params q = shard_params(&p, k, n);
+            if ((rc = ptg_resolve_device(m->shards[k].ctx, &q, done, m->shards[k].slab, m->shards[k].stream)))
+                return rc;
+        }
+        if ((rc = gather_unshard(m, &p, slab_elems)))
             return rc;
     }
-    if ((rc = gather_unshard(m, &p, slab_elems)))
-        return rc;
     const size_t image_elems = (size_t)p.width * p.height * 3;
     for (size_t i = 0; i < image_elems; ++i)
         image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
@@ -944,8 +1086,22 @@ int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_
     return PTG_OK;
 }
 
-int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
-                              double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report)
+int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
+                              double *image_rgb, ptg_noise_report *report)
+{
+    return render_to_noise_on(m, params, target, nullptr, /*filter=*/false, image_rgb, report);
+}
+
+int ptg_multi_render_to_noise_denoised(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
+                                       const ptg_denoise_params *denoise, double *image_rgb, ptg_noise_report *report)
+{
+    return render_to_noise_on(m, params, target, denoise, /*filter=*/true, image_rgb, report);
+}
+
+// ptg_multi_render_adaptive, and with `filter` ptg_multi_render_adaptive_denoised
+static int render_adaptive_on(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
+                              const ptg_denoise_params *denoise, bool filter, double *image_rgb,
+                              int32_t *sample_counts, ptg_adaptive_report *report)
 {
     if (!image_rgb || !target)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_adaptive: NULL image or target");
@@ -956,6 +1112,9 @@ int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_
         return rc;
     if (target->dilate < 0 || target->dilate > 8)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_adaptive: dilate must be in [0, 8]");
+    ptg_denoise_params dk{};
+    if (filter && (rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &dk)))
+        return rc;
     m->timed = false;
     DeviceGuard g;
     ptg_adaptive_report rep{};
@@ -995,7 +1154,8 @@ int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_
             break;
         active = st[4];
     }
-    if ((rc = multi_resolve_active(m, &p)) || (sample_counts && (rc = multi_read_counts(m, &p, sample_counts))))
+    if ((rc = filter ? multi_resolve_filtered(m, &p, 0, dk) : multi_resolve_active(m, &p)) ||
+        (sample_counts && (rc = multi_read_counts(m, &p, sample_counts))))
         return rc;
     if (count) {
         const int n = (int)m->shards.size();
@@ -1016,6 +1176,85 @@ int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_
         image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
     if (report)
         *report = rep;
+    return PTG_OK;
+}
+
+int ptg_multi_render_adaptive(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
+                              double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report)
+{
+    return render_adaptive_on(m, params, target, nullptr, /*filter=*/false, image_rgb, sample_counts, report);
+}
+
+int ptg_multi_render_adaptive_denoised(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
+                                       const ptg_denoise_params *denoise, double *image_rgb, int32_t *sample_counts,
+                                       ptg_adaptive_report *report)
+{
+    return render_adaptive_on(m, params, target, denoise, /*filter=*/true, image_rgb, sample_counts, report);
+}
+
+// the filter's arguments of the pieces and of ptg_multi_render_denoised, after the frame's
+static int check_filtered(const ptg_multi *m, const ptg_params *params, int32_t samples_done, const void *image,
+                          const ptg_denoise_params *denoise, const char *who, ptg_denoise_params *k)
+{
+    if (!image)
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": image is NULL");
+    if (samples_done < 2 || samples_done > params->samples)
+        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": samples must be in [2, params->samples] (the "
+                                                                 "variance needs two)");
+    return ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, k);
+}
+
+int ptg_multi_resolve_denoised(ptg_multi *m, const ptg_params *params, int32_t samples_done,
+                               const ptg_denoise_params *denoise, float *image_rgb)
+{
+    ptg_denoise_params k;
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_filtered(m, params, samples_done, image_rgb, denoise, "multi_resolve_denoised", &k)))
+        return rc;
+    m->timed = false;  // the image / events no longer describe a frame_device frame
+    DeviceGuard g;
+    if ((rc = multi_resolve_filtered(m, params, samples_done, k)))
+        return rc;
+    std::copy(m->host.begin(), m->host.begin() + (size_t)params->width * params->height * 3, image_rgb);
+    return PTG_OK;
+}
+
+int ptg_multi_resolve_active_denoised(ptg_multi *m, const ptg_params *params, const ptg_denoise_params *denoise,
+                                      float *image_rgb)
+{
+    ptg_denoise_params k;
+    int rc = check_frame(m, params);
+    if (rc)
+        return rc;
+    if (!image_rgb)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_resolve_active_denoised: image is NULL");
+    if ((rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &k)))
+        return rc;
+    m->timed = false;
+    DeviceGuard g;
+    if ((rc = multi_resolve_filtered(m, params, 0, k)))
+        return rc;
+    std::copy(m->host.begin(), m->host.begin() + (size_t)params->width * params->height * 3, image_rgb);
+    return PTG_OK;
+}
+
+int ptg_multi_render_denoised(ptg_multi *m, const ptg_params *params, const ptg_denoise_params *denoise,
+                              double *image_rgb)
+{
+    ptg_denoise_params k;
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_filtered(m, params, params->samples, image_rgb, denoise, "multi_render_denoised", &k)))
+        return rc;
+    m->timed = false;
+    DeviceGuard g;
+    ptg_params p = *params;
+    p.flags |= PTG_FLAG_MOMENTS;
+    if ((rc = ptg_multi_reset_accumulation(m, &p)) || (rc = ptg_multi_accumulate(m, &p, 0, p.samples)) ||
+        (rc = multi_resolve_filtered(m, &p, p.samples, k)))
+        return rc;
+    const size_t image_elems = (size_t)p.width * p.height * 3;
+    for (size_t i = 0; i < image_elems; ++i)
+        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
     return PTG_OK;
 }
 
@@ -1209,6 +1448,79 @@ int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const
     if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
         return rc;
     rc = ptg_multi_render_adaptive(m, params, target, image_rgb, sample_counts, report);
+    ptg_multi_destroy(m);
+    return rc;
+}
+
+// the filter's parameters of a one-shot form, checked before any device work
+static int check_denoise_one_shot(const ptg_camera *cam, const ptg_params *params, const ptg_denoise_params *denoise)
+{
+    ptg_denoise_params k;
+    return ptg_denoise_params_for_(cam, params->width, params->height, denoise, &k);
+}
+
+int ptg_render_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                              const ptg_params *params, const int *devices, int n_devices,
+                              const ptg_denoise_params *denoise, double *image_rgb)
+{
+    if (!params || !image_rgb || !cam || !devices || n_devices < 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised_multi: NULL argument or no device");
+    int rc = check_frame_params(params);  // argument checks before any device work
+    if (rc)
+        return rc;
+    if (params->samples < 2)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised_multi: samples must be >= 2 (the variance needs two)");
+    if ((rc = check_denoise_one_shot(cam, params, denoise)))
+        return rc;
+    ptg_multi *m = nullptr;
+    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
+        return rc;
+    rc = ptg_multi_render_denoised(m, params, denoise, image_rgb);
+    ptg_multi_destroy(m);
+    return rc;
+}
+
+int ptg_render_to_noise_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                                       const ptg_params *params, const int *devices, int n_devices,
+                                       const ptg_noise_target *target, const ptg_denoise_params *denoise,
+                                       double *image_rgb, ptg_noise_report *report)
+{
+    if (!params || !image_rgb || !target || !cam || !devices || n_devices < 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise_denoised_multi: NULL argument or no device");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    int rc = check_frame_params(params);  // argument checks before any device work
+    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
+                                 "render_to_noise_denoised_multi", ends, &n_ends)) ||
+        (rc = check_denoise_one_shot(cam, params, denoise)))
+        return rc;
+    ptg_multi *m = nullptr;
+    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
+        return rc;
+    rc = ptg_multi_render_to_noise_denoised(m, params, target, denoise, image_rgb, report);
+    ptg_multi_destroy(m);
+    return rc;
+}
+
+int ptg_render_adaptive_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                                       const ptg_params *params, const int *devices, int n_devices,
+                                       const ptg_adaptive_target *target, const ptg_denoise_params *denoise,
+                                       double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report)
+{
+    if (!params || !image_rgb || !target || !cam || !devices || n_devices < 1)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised_multi: NULL argument or no device");
+    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
+    int rc = check_frame_params(params);  // argument checks before any device work
+    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
+                                 "render_adaptive_denoised_multi", ends, &n_ends)))
+        return rc;
+    if (target->dilate < 0 || target->dilate > 8)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised_multi: dilate must be in [0, 8]");
+    if ((rc = check_denoise_one_shot(cam, params, denoise)))
+        return rc;
+    ptg_multi *m = nullptr;
+    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
+        return rc;
+    rc = ptg_multi_render_adaptive_denoised(m, params, target, denoise, image_rgb, sample_counts, report);
     ptg_multi_destroy(m);
     return rc;
 }

@@ -2429,6 +2429,44 @@ __global__ __launch_bounds__(256) void select_over_kernel(KArgs A, const unsigne
     reduce_noise_stats(over, cnt, fixed, rho_bits, stats);
 }
 
+// ptg_noise_active_device: noise_kernel's variance slab and rho with each
+// pixel's own sample count n_p, the filter's guide for an adaptive frame (one
+// thread per slab pixel, grid-stride; var and rho_out each optional).
+// n_p < 2 knows nothing beyond the clamp's bound: rho = +inf as in
+// select_over_kernel, and per channel the V noise_pixel yields when every
+// sub-pixel's variance sits at the 1/4 cap.  No statistics: the select step
+// supplies them.
+__global__ __launch_bounds__(256) void noise_active_kernel(KArgs A, const unsigned long long *__restrict__ acc2,
+                                                           const int *__restrict__ counts, double floor,
+                                                           float *__restrict__ var, float *__restrict__ rho_out)
+{
+    const long long total = (long long)A.slab_rows * A.W;
+    const long long stride = (long long)gridDim.x * 256;
+    const float v_cap = (float)(((double)A.inv_sub2 * (double)A.inv_sub2) * ((double)A.lanes_per_pixel * 0.25));
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        if (out_row_of(A, (int)(i / A.W)) >= A.H)
+            continue;  // a slab row past the image
+        const int np = counts[i];
+        float rho = __builtin_inff();
+        float v[3] = {v_cap, v_cap, v_cap};
+        if (np >= 2) {
+            double V[3];
+            rho = noise_pixel(A, A.acc + (size_t)i * A.lanes_per_pixel * 3, acc2 + (size_t)i * A.lanes_per_pixel * 3,
+                              (double)np, floor, V);
+            v[0] = (float)V[0];
+            v[1] = (float)V[1];
+            v[2] = (float)V[2];
+        }
+        if (var) {
+            var[(size_t)i * 3 + 0] = v[0];
+            var[(size_t)i * 3 + 1] = v[1];
+            var[(size_t)i * 3 + 2] = v[2];
+        }
+        if (rho_out)
+            rho_out[i] = rho;
+    }
+}
+
 // List building, step 1: one workgroup per slab row writes the row's active x
 // in ascending order to list[row * W ...] and their number to row_count[row].
 // Active: flags == NULL, or some flag byte of the pixel's (2 dilate + 1)^2
@@ -3685,6 +3723,30 @@ int ptg_select_over_device(ptg_context *ctx, const ptg_params *params, double re
     const long long blocks = (pixels + 255) / 256;  // the kernel strides over the rest
     select_over_kernel<<<(unsigned)(blocks < kNoiseBlocks ? blocks : kNoiseBlocks), 256, 0, s>>>(
         A, ctx->d_acc2, ctx->d_counts, rel_error, floor, d_over, d_rho, d_stats);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_noise_active_device(ptg_context *ctx, const ptg_params *params, double floor, float *d_var, float *d_rho,
+                            void *stream)
+{
+    if (!ctx)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL context");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (!(floor > 0.0))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "noise_active: floor must be > 0");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    if ((rc = begin_adaptive(ctx, params, A, s, "noise_active")))
+        return rc;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    if (pixels <= 0 || (!d_var && !d_rho))
+        return PTG_OK;
+    const long long blocks = (pixels + 255) / 256;  // the kernel strides over the rest
+    noise_active_kernel<<<(unsigned)(blocks < kNoiseBlocks ? blocks : kNoiseBlocks), 256, 0, s>>>(
+        A, ctx->d_acc2, ctx->d_counts, floor, d_var, d_rho);
     PTG_HIP(hipGetLastError());
     return PTG_OK;
 }

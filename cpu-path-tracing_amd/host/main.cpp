@@ -9,7 +9,7 @@
 //                 [--light-sampling]
 //                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]
 //                  [--adaptive [--dilate D] [--spp-map FILE]]]
-//                 [--denoise [--denoise-iterations N]] [--features-out PREFIX]
+//                 [--denoise | --filter [--denoise-iterations N]] [--features-out PREFIX]
 //
 //   spp      total samples per pixel (main.cpp:206: divided by the 4 sub-pixels), default 4
 //   scene    box_mirror (the reference binary's scene, main.cpp:25,208) | box | simple |
@@ -50,7 +50,15 @@
 //            --noise-target the filter runs on the frame at the spp the "noise:" line reports
 //            (ptg_render_to_noise_denoised: the passes carry the moments, nothing is rendered
 //            twice).  With --adaptive, or with a --devices list of several: exit status 2
-//            (DESIGN.md "Denoising", out of scope).
+//            (--denoise is the one-device, uniform-count driver: use --filter).
+//   --filter  the same filter on whatever frame was rendered: plain, --noise-target or
+//            --adaptive (its variance then from every pixel's own sample count,
+//            ptg_render_adaptive_denoised; --spp-map keeps working), on any --devices list (the
+//            shards' colour and variance are gathered on the first device, which filters the
+//            frame once: ptg_render_denoised_multi and its siblings).  The image is the same bit
+//            for bit for any device list; alone on one device it is --denoise's.  Takes
+//            --denoise-iterations, needs --spp >= 8, and does not combine with --denoise (exit
+//            status 2).
 //   --features-out PREFIX  the first-hit features of every pixel (ptg_features; no RNG, the
 //            sub-pixel centres): PREFIX_normal.ppm (P6, round((n + 1) / 2 * 255) per axis, the
 //            mean facing normal; sky 0 0 0 -> 128 128 128), PREFIX_albedo.ppm (P6, round(a * 255),
@@ -178,7 +186,7 @@ int main(int argc, char *argv[])
     bool to_noise = false, adaptive = false;
     int min_spp = 64, dilate = 1;
     std::string spp_map;
-    bool denoise = false;
+    bool denoise = false, filter = false;
     int denoise_iterations = -1;  // -1: the default
     std::string features_out;
     ptg_noise_target target{};
@@ -247,6 +255,8 @@ int main(int argc, char *argv[])
                 spp_map = val();
             else if (a == "--denoise")
                 denoise = true;
+            else if (a == "--filter")
+                filter = true;
             else if (a == "--denoise-iterations")
                 denoise_iterations = std::atoi(val().c_str());
             else if (a == "--features-out")
@@ -266,20 +276,26 @@ int main(int argc, char *argv[])
         return 2;
     }
     int const samps = spp / (num_subpixels * num_subpixels);
-    if (denoise_iterations != -1 && (!denoise || denoise_iterations < 0 || denoise_iterations > 8)) {
-        std::fprintf(stderr, "--denoise-iterations needs --denoise and a value in 0..8\n");
+    if (denoise_iterations != -1 && ((!denoise && !filter) || denoise_iterations < 0 || denoise_iterations > 8)) {
+        std::fprintf(stderr, "--denoise-iterations needs --denoise or --filter and a value in 0..8\n");
+        return 2;
+    }
+    if (denoise && filter) {
+        std::fprintf(stderr, "--filter and --denoise do not combine (--filter alone is --denoise on any frame)\n");
         return 2;
     }
     if (denoise && adaptive) {
-        std::fprintf(stderr, "--denoise does not combine with --adaptive (the pixels hold different sample counts)\n");
+        std::fprintf(stderr, "--denoise does not combine with --adaptive (the pixels hold different sample counts): "
+                             "use --filter\n");
         return 2;
     }
     if (denoise && parse_devices(devices).size() != 1) {
-        std::fprintf(stderr, "--denoise renders on one device (--devices %s)\n", devices.c_str());
+        std::fprintf(stderr, "--denoise renders on one device (--devices %s): use --filter\n", devices.c_str());
         return 2;
     }
-    if (denoise && render && samps < 2) {
-        std::fprintf(stderr, "--denoise needs --spp >= 8 (two samples per sub-pixel for the variance)\n");
+    if ((denoise || filter) && render && samps < 2) {
+        std::fprintf(stderr, "%s needs --spp >= 8 (two samples per sub-pixel for the variance)\n",
+                     filter ? "--filter" : "--denoise");
         return 2;
     }
 
@@ -315,7 +331,7 @@ int main(int argc, char *argv[])
     auto const t0 = std::chrono::steady_clock::now();
     int rc = PTG_OK;
     int samps_done = samps;
-    // --denoise: the filter's defaults, the pixel spread from the camera
+    // --denoise, --filter: the filter's defaults, the pixel spread from the camera
     ptg_denoise_params dn{};
     ptg_denoise_defaults(&dn);
     dn.pixel_spread = 0.0f;
@@ -351,11 +367,18 @@ int main(int argc, char *argv[])
             ptg_adaptive_target const at{target.rel_error, target.floor, target.max_fraction, target.min_samples, dilate};
             ptg_adaptive_report rep{};
             std::vector<std::int32_t> counts;
-            rc = nd > 1 ? pt::gpu::render_image_adaptive(some_scene, cam, image, width, height, samps, at, rep, devs,
-                                                         spp_map.empty() ? nullptr : &counts, num_subpixels, seed, flags)
-                        : pt::gpu::render_image_adaptive(some_scene, cam, image, width, height, samps, at, rep,
-                                                         spp_map.empty() ? nullptr : &counts, num_subpixels, seed,
-                                                         devs[0], flags);
+            std::vector<std::int32_t> *const cnt = spp_map.empty() ? nullptr : &counts;
+            if (filter)
+                rc = nd > 1 ? pt::gpu::render_image_adaptive_denoised(some_scene, cam, image, width, height, samps, at,
+                                                                      rep, devs, cnt, &dn, num_subpixels, seed, flags)
+                            : pt::gpu::render_image_adaptive_denoised(some_scene, cam, image, width, height, samps, at,
+                                                                      rep, cnt, &dn, num_subpixels, seed, devs[0],
+                                                                      flags);
+            else
+                rc = nd > 1 ? pt::gpu::render_image_adaptive(some_scene, cam, image, width, height, samps, at, rep, devs,
+                                                             cnt, num_subpixels, seed, flags)
+                            : pt::gpu::render_image_adaptive(some_scene, cam, image, width, height, samps, at, rep, cnt,
+                                                             num_subpixels, seed, devs[0], flags);
             if (rc == PTG_OK) {
                 samps_done = rep.max_samples;
                 double const mean = rep.pixels ? double(rep.total_samples) / double(rep.pixels) : 0.0;
@@ -380,7 +403,10 @@ int main(int argc, char *argv[])
             }
         } else {
             ptg_noise_report rep{};
-            if (denoise)  // (one device: checked above) the frame it stops at, filtered
+            if (filter && nd > 1)
+                rc = pt::gpu::render_image_to_noise_denoised(some_scene, cam, image, width, height, samps, target, rep,
+                                                             devs, &dn, num_subpixels, seed, flags);
+            else if (denoise || filter)  // one device (--denoise: checked above): the frame it stops at, filtered
                 rc = pt::gpu::render_image_to_noise_denoised(some_scene, cam, image, width, height, samps, target, rep,
                                                              &dn, num_subpixels, seed, devs[0], flags);
             else if (nd > 1)
@@ -399,7 +425,10 @@ int main(int argc, char *argv[])
                              target.rel_error, rep.max_rho, rep.mean_rho, rep.converged);
             }
         }
-    } else if (denoise) {
+    } else if (filter && nd != 1) {
+        rc = pt::gpu::render_image_denoised(some_scene, cam, image, width, height, samps, devs, &dn, num_subpixels, seed,
+                                            flags);
+    } else if (denoise || filter) {
         rc = pt::gpu::render_image_denoised(some_scene, cam, image, width, height, samps, &dn, num_subpixels, seed,
                                             devs[0], flags);
     } else if (nd == 1 && devs[0] < 0) {  // main.cpp:214-236 replaced by one call

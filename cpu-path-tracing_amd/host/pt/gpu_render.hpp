@@ -217,6 +217,95 @@ inline int render_image_to_noise_denoised(scene const &scn, camera const &cam, s
                                         reinterpret_cast<double *>(image.data()), &report);
 }
 
+namespace detail {
+inline ptg_params frame_params(int width, int height, int samps, int num_subpixels, std::uint64_t seed, int flags)
+{
+    ptg_params p{};
+    p.width = width;
+    p.height = height;
+    p.samples = samps;
+    p.num_subpixels = num_subpixels;
+    p.seed = seed;
+    p.band_rows = 1;
+    p.shard_rank = 0;
+    p.shard_count = 1;
+    p.flags = flags;
+    return p;
+}
+}  // namespace detail
+
+// render_image_adaptive whose frame goes through the filter, guided by the
+// variance of each pixel at its own sample count
+// (ptg_render_adaptive_denoised); report and counts are render_image_adaptive's.
+inline int render_image_adaptive_denoised(scene const &scn, camera const &cam, std::vector<vec3> &image, int width,
+                                          int height, int samps, ptg_adaptive_target const &target,
+                                          ptg_adaptive_report &report, std::vector<std::int32_t> *sample_counts = nullptr,
+                                          ptg_denoise_params const *denoise = nullptr, int num_subpixels = 2,
+                                          std::uint64_t seed = default_seed, int device = -1, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    if (sample_counts)
+        sample_counts->assign(image.size(), 0);
+    ptg_params const p = detail::frame_params(width, height, samps, num_subpixels, seed, flags);
+    return ptg_render_adaptive_denoised(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                                        reinterpret_cast<ptg_camera const *>(&cam), &p, device, &target, denoise,
+                                        reinterpret_cast<double *>(image.data()),
+                                        sample_counts ? sample_counts->data() : nullptr, &report);
+}
+
+// The three denoised drivers on several GPUs of this process
+// (ptg_render_denoised_multi / ptg_render_to_noise_denoised_multi /
+// ptg_render_adaptive_denoised_multi): the shards' colour and variance slabs
+// are gathered on the first device, which filters the frame once; the image
+// equals the one-device overloads' bit for bit for any device list.
+inline int render_image_denoised(scene const &scn, camera const &cam, std::vector<vec3> &image, int width, int height,
+                                 int samps, std::vector<int> const &devices, ptg_denoise_params const *denoise = nullptr,
+                                 int num_subpixels = 2, std::uint64_t seed = default_seed, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    ptg_params const p = detail::frame_params(width, height, samps, num_subpixels, seed, flags);
+    return ptg_render_denoised_multi(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                                     reinterpret_cast<ptg_camera const *>(&cam), &p, devices.data(),
+                                     static_cast<int>(devices.size()), denoise,
+                                     reinterpret_cast<double *>(image.data()));
+}
+
+inline int render_image_to_noise_denoised(scene const &scn, camera const &cam, std::vector<vec3> &image, int width,
+                                          int height, int samps, ptg_noise_target const &target,
+                                          ptg_noise_report &report, std::vector<int> const &devices,
+                                          ptg_denoise_params const *denoise = nullptr, int num_subpixels = 2,
+                                          std::uint64_t seed = default_seed, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    ptg_params const p = detail::frame_params(width, height, samps, num_subpixels, seed, flags);
+    return ptg_render_to_noise_denoised_multi(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()),
+                                              scn.spheres.size(), reinterpret_cast<ptg_camera const *>(&cam), &p,
+                                              devices.data(), static_cast<int>(devices.size()), &target, denoise,
+                                              reinterpret_cast<double *>(image.data()), &report);
+}
+
+inline int render_image_adaptive_denoised(scene const &scn, camera const &cam, std::vector<vec3> &image, int width,
+                                          int height, int samps, ptg_adaptive_target const &target,
+                                          ptg_adaptive_report &report, std::vector<int> const &devices,
+                                          std::vector<std::int32_t> *sample_counts = nullptr,
+                                          ptg_denoise_params const *denoise = nullptr, int num_subpixels = 2,
+                                          std::uint64_t seed = default_seed, int flags = 0)
+{
+    if (image.size() != static_cast<std::size_t>(width) * static_cast<std::size_t>(height))
+        return PTG_ERR_INVALID_ARGUMENT;
+    if (sample_counts)
+        sample_counts->assign(image.size(), 0);
+    ptg_params const p = detail::frame_params(width, height, samps, num_subpixels, seed, flags);
+    return ptg_render_adaptive_denoised_multi(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()),
+                                              scn.spheres.size(), reinterpret_cast<ptg_camera const *>(&cam), &p,
+                                              devices.data(), static_cast<int>(devices.size()), &target, denoise,
+                                              reinterpret_cast<double *>(image.data()),
+                                              sample_counts ? sample_counts->data() : nullptr, &report);
+}
+
 // The first-hit feature frame (ptg_features): width * height * 12 floats in the
 // image's row order, {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0} per pixel.
 inline int feature_frame(scene const &scn, camera const &cam, std::vector<float> &features, int width, int height,

@@ -33,6 +33,10 @@ EXPORTS = (
     "ptg_light_list",
     "ptg_features_device", "ptg_denoise_defaults", "ptg_pixel_spread", "ptg_denoise_scratch_bytes",
     "ptg_denoise_device", "ptg_denoise_host", "ptg_render_denoised", "ptg_render_to_noise_denoised", "ptg_features",
+    "ptg_noise_active_device", "ptg_render_adaptive_denoised",
+    "ptg_multi_resolve_denoised", "ptg_multi_resolve_active_denoised", "ptg_multi_render_denoised",
+    "ptg_multi_render_to_noise_denoised", "ptg_multi_render_adaptive_denoised", "ptg_render_denoised_multi",
+    "ptg_render_to_noise_denoised_multi", "ptg_render_adaptive_denoised_multi",
 )
 
 
@@ -173,6 +177,24 @@ def lib():
             "ptg_render_to_noise_denoised": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(NoiseTarget),
                                                  C.POINTER(DenoiseParams), P, C.POINTER(NoiseReport)]),
             "ptg_features": (I, [P, C.c_size_t, P, C.POINTER(Params), I, P]),
+            "ptg_noise_active_device": (I, [P, C.POINTER(Params), C.c_double, P, P, P]),
+            "ptg_render_adaptive_denoised": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(AdaptiveTarget),
+                                                 C.POINTER(DenoiseParams), P, P, C.POINTER(AdaptiveReport)]),
+            "ptg_multi_resolve_denoised": (I, [P, C.POINTER(Params), C.c_int32, C.POINTER(DenoiseParams), P]),
+            "ptg_multi_resolve_active_denoised": (I, [P, C.POINTER(Params), C.POINTER(DenoiseParams), P]),
+            "ptg_multi_render_denoised": (I, [P, C.POINTER(Params), C.POINTER(DenoiseParams), P]),
+            "ptg_multi_render_to_noise_denoised": (I, [P, C.POINTER(Params), C.POINTER(NoiseTarget),
+                                                       C.POINTER(DenoiseParams), P, C.POINTER(NoiseReport)]),
+            "ptg_multi_render_adaptive_denoised": (I, [P, C.POINTER(Params), C.POINTER(AdaptiveTarget),
+                                                       C.POINTER(DenoiseParams), P, P, C.POINTER(AdaptiveReport)]),
+            "ptg_render_denoised_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I,
+                                              C.POINTER(DenoiseParams), P]),
+            "ptg_render_to_noise_denoised_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I,
+                                                       C.POINTER(NoiseTarget), C.POINTER(DenoiseParams), P,
+                                                       C.POINTER(NoiseReport)]),
+            "ptg_render_adaptive_denoised_multi": (I, [P, C.c_size_t, P, C.POINTER(Params), C.POINTER(C.c_int), I,
+                                                       C.POINTER(AdaptiveTarget), C.POINTER(DenoiseParams), P, P,
+                                                       C.POINTER(AdaptiveReport)]),
             # internal (tests, tools): ptg_denoise_device with the kernel named (0 tiled where it fits, 1 plain)
             "ptg_denoise_device_kernel_": (I, [P, P, P, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), P, P, P,
                                                C.c_size_t, P, I]),

@@ -10,6 +10,10 @@
 * render_denoised(...),  -- render() followed by the variance-guided a-trous
   denoise(...)              filter (first-hit features from Context.features);
                             denoise() filters device tensors the caller holds.
+                            render_adaptive_denoised() filters an adaptive
+                            frame (variance from each pixel's own count), and
+                            MultiContext.render_*_denoised() frames sharded
+                            over several GPUs, bit for bit the same image.
 * Context                -- device-resident scene for repeated renders into
                             torch CUDA tensors (bench, multi-GPU).
 * render_sharded(...)    -- one process per GPU: each rank renders its
@@ -385,6 +389,65 @@ class MultiContext:
         out = _adaptive_report(rep)
         return (out, counts) if sample_counts else out
 
+    # ---- denoised frames over all devices (ptg_multi_resolve_denoised ... ptg_multi_render_adaptive_denoised):
+    # the filtered image equals the one-device driver's bit for bit for any device count, band_rows and dilate
+    @staticmethod
+    def _dn(denoise):
+        return C.byref(denoise) if denoise is not None else None
+
+    def resolve_denoised(self, image: np.ndarray, params: Params, samples_done: int,
+                         denoise: Optional[DenoiseParams] = None) -> np.ndarray:
+        """The sums of accumulate() passes with FLAG_MOMENTS, resolved at
+        samples_done (>= 2) and filtered on the root, written to `image`
+        (float32); the sums are kept.  denoise None: the defaults with the
+        camera's pixel_spread."""
+        check(lib().ptg_multi_resolve_denoised(self._h, C.byref(params), int(samples_done), self._dn(denoise),
+                                               self._image(image, params, np.float32)), "ptg_multi_resolve_denoised")
+        return image
+
+    def resolve_active_denoised(self, image: np.ndarray, params: Params,
+                                denoise: Optional[DenoiseParams] = None) -> np.ndarray:
+        """resolve_active() through the filter, its variance from each
+        pixel's own count (Context.noise_active); the sums, counts and active
+        lists are kept."""
+        check(lib().ptg_multi_resolve_active_denoised(self._h, C.byref(params), self._dn(denoise),
+                                                      self._image(image, params, np.float32)),
+              "ptg_multi_resolve_active_denoised")
+        return image
+
+    def render_denoised(self, image: np.ndarray, params: Params, denoise: Optional[DenoiseParams] = None) -> np.ndarray:
+        """render_denoised() over all devices (added into `image`, float64)."""
+        check(lib().ptg_multi_render_denoised(self._h, C.byref(params), self._dn(denoise),
+                                              self._image(image, params, np.float64)), "ptg_multi_render_denoised")
+        return image
+
+    def render_to_noise_denoised(self, image: np.ndarray, params: Params, rel_error: float, floor: float = 0.01,
+                                 max_fraction: float = 0.01, min_samples: int = 16,
+                                 denoise: Optional[DenoiseParams] = None) -> dict:
+        """render_to_noise_denoised() over all devices (added into `image`,
+        float64); render_to_noise()'s report."""
+        target = NoiseTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), 0)
+        rep = NoiseReport()
+        check(lib().ptg_multi_render_to_noise_denoised(self._h, C.byref(params), C.byref(target), self._dn(denoise),
+                                                       self._image(image, params, np.float64), C.byref(rep)),
+              "ptg_multi_render_to_noise_denoised")
+        return _noise_report(rep)
+
+    def render_adaptive_denoised(self, image: np.ndarray, params: Params, rel_error: float, floor: float = 0.01,
+                                 max_fraction: float = 0.01, min_samples: int = 16, dilate: int = 1,
+                                 sample_counts: bool = False, denoise: Optional[DenoiseParams] = None):
+        """render_adaptive_denoised() over all devices (added into `image`,
+        float64); render_adaptive()'s report (and counts)."""
+        target = AdaptiveTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), int(dilate))
+        rep = AdaptiveReport()
+        counts = np.zeros((params.height, params.width), dtype=np.int32) if sample_counts else None
+        check(lib().ptg_multi_render_adaptive_denoised(self._h, C.byref(params), C.byref(target), self._dn(denoise),
+                                                       self._image(image, params, np.float64),
+                                                       counts.ctypes.data_as(C.c_void_p) if sample_counts else None,
+                                                       C.byref(rep)), "ptg_multi_render_adaptive_denoised")
+        out = _adaptive_report(rep)
+        return (out, counts) if sample_counts else out
+
 
 # every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel)
 KERNEL_SOURCES = ("ptg_render.hip", "pt_device.hpp", "bvh_build.hpp", "kernel_args.hpp", "scene_prep.hpp",
@@ -663,6 +726,20 @@ class Context:
         check(lib().ptg_read_sample_counts_device(self._h, C.byref(params), C.c_void_p(counts.data_ptr()),
                                                   C.c_void_p(self._stream(stream))), "ptg_read_sample_counts_device")
 
+    def noise_active(self, params: Params, floor: float, var=None, rho=None, stream=None) -> None:
+        """noise()'s `var` and `rho` with each pixel's own sample count (the
+        guide of denoise() for an adaptive frame); a pixel with fewer than 2
+        samples gets rho = +inf and the variance of the clamp's bound, 1 / (4
+        num_subpixels^2) per channel.  The sums, counts and list are kept."""
+        import torch
+        if var is not None:
+            self._check(var, torch.float32, self._pixels(params) * 3)
+        if rho is not None:
+            self._check(rho, torch.float32, self._pixels(params))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        check(lib().ptg_noise_active_device(self._h, C.byref(params), float(floor), ptr(var), ptr(rho),
+                                            C.c_void_p(self._stream(stream))), "ptg_noise_active_device")
+
     # ---- denoising (ptg_features_device; the filter itself needs no context: denoise())
     def features(self, params: Params, out=None, stream=None):
         """The first-hit features of every slab pixel (float32, slab rows*W*12:
@@ -847,6 +924,32 @@ def render_to_noise_denoised(scn, cam, image: np.ndarray, width: int, height: in
                                              image.ctypes.data_as(C.c_void_p), C.byref(rep)),
           "ptg_render_to_noise_denoised")
     return _noise_report(rep)
+
+
+def render_adaptive_denoised(scn, cam, image: np.ndarray, width: int, height: int, samples: int, rel_error: float,
+                             floor: float = 0.01, max_fraction: float = 0.01, min_samples: int = 16, dilate: int = 1,
+                             num_subpixels: int = 2, seed: int = DEFAULT_SEED, device: int = -1, flags: int = 0,
+                             sample_counts: bool = False, params: Optional[DenoiseParams] = None):
+    """ptg_render_adaptive_denoised: render_adaptive() whose frame goes
+    through the filter, guided by the variance of each pixel at its own sample
+    count (Context.noise_active).  Returns render_adaptive()'s report, or
+    (report, counts) with sample_counts=True."""
+    sp = _spheres_array(scn)
+    ca = _camera_array(cam)
+    if image.dtype != np.float64 or not image.flags["C_CONTIGUOUS"] or image.size != width * height * 3:
+        raise ValueError("image must be a C-contiguous float64 array of width*height*3 values")
+    p = make_params(width, height, samples, num_subpixels, seed, flags=flags)
+    target = AdaptiveTarget(float(rel_error), float(floor), float(max_fraction), int(min_samples), int(dilate))
+    rep = AdaptiveReport()
+    counts = np.zeros((height, width), dtype=np.int32) if sample_counts else None
+    check(lib().ptg_render_adaptive_denoised(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
+                                             C.byref(p), int(device), C.byref(target),
+                                             C.byref(params) if params is not None else None,
+                                             image.ctypes.data_as(C.c_void_p),
+                                             counts.ctypes.data_as(C.c_void_p) if sample_counts else None,
+                                             C.byref(rep)), "ptg_render_adaptive_denoised")
+    out = _adaptive_report(rep)
+    return (out, counts) if sample_counts else out
 
 
 def features(scn, cam, width: int, height: int, num_subpixels: int = 2, device: int = -1) -> np.ndarray:

@@ -652,6 +652,87 @@ int ptg_render_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_c
 int ptg_render_to_noise_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
                                  const ptg_params *params, int device, const ptg_noise_target *target,
                                  const ptg_denoise_params *denoise, double *image_rgb, ptg_noise_report *report);
+/* ---- denoising adaptive frames and frames on several GPUs ---------------
+ * ptg_noise_active_device: the variance slab and rho of ptg_noise_device with
+ * each pixel's own sample count n_p in place of samples_done -- the V and rho
+ * ptg_select_over_device uses internally, the filter's guide for a frame whose
+ * pixels stopped at different counts.  d_var (slab_rows * width * 3 floats)
+ * and d_rho (slab_rows * width floats) are each optional; slab rows past the
+ * image are left untouched; asynchronous on stream; the sums, the counts and
+ * the active list are left alone.  n_p < 2 is defined, not an error: rho =
+ * +inf as in the select step, and per channel V is the value the definition
+ * yields when every sub-pixel's variance sits at the 1/4 cap,
+ * (float)(inv_sub2^2 (num_subpixels^2 0.25)) in its double arithmetic:
+ * nothing is known beyond the clamp's bound.  State rules as
+ * ptg_select_active_device's (PTG_ERR_INVALID_ARGUMENT after a
+ * ptg_accumulate_device pass until the next reset, and for floor <= 0); any
+ * shard_count.  ptg_noise_device keeps refusing adaptive sums. */
+int ptg_noise_active_device(ptg_context *ctx, const ptg_params *params, double floor, float *d_var, float *d_rho,
+                            void *stream);
+
+/* ptg_render_adaptive, then the filter on the frame it stopped at: the same
+ * schedule, stop rule, report and counts; then ptg_resolve_active_device,
+ * ptg_noise_active_device, ptg_features_device, ptg_denoise_device, and the
+ * ADD into image_rgb in ptg_render's row order.  denoise NULL or pixel_spread
+ * 0 as in ptg_render_denoised.  With iterations = 0 the image, the counts and
+ * the report equal ptg_render_adaptive's bit for bit.  PTG_FLAG_EXACT_MATH and
+ * PTG_FLAG_LIGHT_SAMPLING are honoured; PTG_FLAG_REFERENCE_F64 is
+ * PTG_ERR_UNSUPPORTED. */
+int ptg_render_adaptive_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                                 const ptg_params *params, int device, const ptg_adaptive_target *target,
+                                 const ptg_denoise_params *denoise, double *image_rgb, int32_t *sample_counts,
+                                 ptg_adaptive_report *report);
+
+/* On a ptg_multi (params->shard_count 1, PTG_FLAG_REFERENCE_F64 refused, the
+ * caller's device restored, a broken context refused, as for the entry points
+ * of "several GPUs" above).  The pieces act on the sums the context holds and
+ * keep them: every shard resolves its slab and writes its variance slab
+ * (ptg_noise_device / ptg_noise_active_device), the root receives the colour
+ * slabs and the variance slabs -- two gathers through the one path; on RCCL
+ * one ncclGather per rank inside a group each, a failure there aborts the
+ * communicators and breaks the context as the frame gather's does -- and
+ * un-shards both; the features of the whole frame come from the root's own
+ * context (they depend on the scene, the camera and the global pixel only, so
+ * nothing is moved; the root shard's sums, counts and active list are not
+ * touched); ONE filter on the root.  W*H*3 floats are written like
+ * ptg_multi_resolve.
+ *   ptg_multi_resolve_denoised: after ptg_multi_accumulate passes with
+ *     PTG_FLAG_MOMENTS; ptg_multi_noise's rules, samples_done >= 2.
+ *   ptg_multi_resolve_active_denoised: while adaptive passes are in the sums;
+ *     ptg_multi_resolve_active's rules.
+ * The drivers ADD into image_rgb like their unfiltered siblings
+ * (ptg_multi_render at samples >= 2 with the moments kept,
+ * ptg_multi_render_to_noise, ptg_multi_render_adaptive), whose report, counts
+ * and kernel counters they return; the *_multi forms are create + the call +
+ * destroy on n_devices distinct GPUs.
+ * The guarantee: for any device count, band_rows and dilate the filtered
+ * image equals the one-device driver's (ptg_render_denoised,
+ * ptg_render_to_noise_denoised, ptg_render_adaptive_denoised) bit for bit:
+ * every input of the filter is bit-identical across shardings and the filter
+ * is one fixed fp32 sequence over the whole frame. */
+int ptg_multi_resolve_denoised(ptg_multi *m, const ptg_params *params, int32_t samples_done,
+                               const ptg_denoise_params *denoise, float *image_rgb);
+int ptg_multi_resolve_active_denoised(ptg_multi *m, const ptg_params *params, const ptg_denoise_params *denoise,
+                                      float *image_rgb);
+int ptg_multi_render_denoised(ptg_multi *m, const ptg_params *params, const ptg_denoise_params *denoise,
+                              double *image_rgb);
+int ptg_multi_render_to_noise_denoised(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
+                                       const ptg_denoise_params *denoise, double *image_rgb, ptg_noise_report *report);
+int ptg_multi_render_adaptive_denoised(ptg_multi *m, const ptg_params *params, const ptg_adaptive_target *target,
+                                       const ptg_denoise_params *denoise, double *image_rgb, int32_t *sample_counts,
+                                       ptg_adaptive_report *report);
+int ptg_render_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                              const ptg_params *params, const int *devices, int n_devices,
+                              const ptg_denoise_params *denoise, double *image_rgb);
+int ptg_render_to_noise_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                                       const ptg_params *params, const int *devices, int n_devices,
+                                       const ptg_noise_target *target, const ptg_denoise_params *denoise,
+                                       double *image_rgb, ptg_noise_report *report);
+int ptg_render_adaptive_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                                       const ptg_params *params, const int *devices, int n_devices,
+                                       const ptg_adaptive_target *target, const ptg_denoise_params *denoise,
+                                       double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report);
+
 /* Host helper: ptg_features_device's frame copied to the host, width *
  * height * 12 floats in ptg_render's row order (row r is the reference's
  * y = height - 1 - r).  Synchronous; params->shard_count must be 1. */
