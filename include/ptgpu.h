@@ -76,7 +76,16 @@ typedef struct ptg_camera {
  * quantised to a u64 fixed-point value q(c) = trunc(c * 2^32) (c clamped to
  * [0, 2^30]) and summed exactly; the sub-pixel mean is
  * (float)((double)sum * 2^-32 / samps).  The image therefore does not depend
- * on scheduling, chunking or sharding. */
+ * on scheduling, chunking or sharding.
+ *
+ * The sum of a (pixel, sub-pixel, channel) is exact while samples x the
+ * largest clipped component stays below 2^32 (the sum below 2^64).  A
+ * component clipped to 2^30 adds 2^62: at most 3 such samples per sum;
+ * a fourth wraps the u64 sum and the sub-pixel goes dark with no error.  The
+ * same bound holds for the second-moment sums of PTG_FLAG_MOMENTS, whose
+ * squares are clipped to 2^30 from components above 2^15.  A caller finds out
+ * with PTG_FLAG_COUNT_NONFINITE: a fourth counter of 0 means that no component
+ * was clipped (by 0 or by 2^30; exactly 2^30 is in range and not counted). */
 typedef struct ptg_params {
     int32_t width;          /* main.cpp:204 */
     int32_t height;         /* main.cpp:205 */
@@ -101,7 +110,9 @@ typedef struct ptg_params {
 /* with PTG_FLAG_COUNT_NONFINITE (implies the counters above), d_segments points
  * to 4 counters; the 4th += paths whose radiance has a component that is NaN,
  * negative or above 2^30 -- values the exact accumulation would clip (NaN and
- * negative to 0).  None are expected: the -m gpu tests assert 0. */
+ * negative to 0).  None are expected in the shipped scenes: the -m gpu tests
+ * assert 0 there, and the oracle's count on scenes built to be out of range
+ * (tests/test_gpu_radiance_range.py). */
 #define PTG_FLAG_COUNT_NONFINITE 2
 /* PTG_FLAG_REFERENCE_F64: render with the reference's own double-precision
  * arithmetic, operation for operation (src/main.cpp:30-197 and the pt

@@ -49,6 +49,7 @@ pytestmark = pytest.mark.gpu
 
 import ptgpu  # noqa: E402
 import pyoracle as po  # noqa: E402
+import range_scenes  # noqa: E402
 import shape_scenes as ss  # noqa: E402
 from test_gpu_noise import _accumulate, _quant, _read, _sums  # noqa: E402
 from test_wall_rules import sunk_scene  # noqa: E402
@@ -66,6 +67,8 @@ def _require_gpu():
 def _scene(name, W, H):
     if name in ss.CASES:
         return ss.make(name, W, H)
+    if name in range_scenes.CASES:  # (tests/test_gpu_radiance_range.py)
+        return range_scenes.make(name, W, H)
     scn = sunk_scene(W, H) if name == "sunk_scene" else ptgpu.make_scene(name, W, H)
     return scn, ptgpu.camera.with_config(scn.camera_parameters)
 
@@ -96,10 +99,14 @@ def test_fast_render_kernel_equals_fast_trace_kernel(name):
     check_render_equals_trace(name, *FRAMES[name])
 
 
-def check_render_equals_trace(name, W, H, n, nsub, passes):
-    """The identity of (a) on one frame (also used by tests/test_gpu_frame_shapes.py)."""
-    p = ptgpu.make_params(W, H, n, nsub, SEED, flags=MOM)
-    plain = ptgpu.make_params(W, H, n, nsub, SEED)
+def check_render_equals_trace(name, W, H, n, nsub, passes, flags=0, count=False):
+    """The identity of (a) on one frame in the mode `flags` (also used by
+    tests/test_gpu_frame_shapes.py and tests/test_gpu_radiance_range.py).  Returns the trace
+    kernel's radiances [H (image row), W, nsub^2, n, 3] and, with `count`, the four counters of
+    the one-shot frame rendered once more with PTG_FLAG_COUNT_NONFINITE (the same image)."""
+    p = ptgpu.make_params(W, H, n, nsub, SEED, flags=flags | MOM)
+    plain = ptgpu.make_params(W, H, n, nsub, SEED, flags=flags)
+    counting = ptgpu.make_params(W, H, n, nsub, SEED, flags=flags | ptgpu.FLAG_COUNT_TESTS | ptgpu.FLAG_COUNT_NONFINITE)
     coords = _frame_coords(W, H, n, nsub)
     with ptgpu.Context(*_scene(name, W, H)) as ctx:
         _accumulate(ctx, p, passes)
@@ -107,6 +114,10 @@ def check_render_equals_trace(name, W, H, n, nsub, passes):
         c, _ = ctx.trace_samples(torch.from_numpy(coords).cuda(), plain)
         shot = torch.full((H * W * 3,), -7.0, dtype=torch.float32, device="cuda")
         ctx.render_device(shot, plain)
+        if count:
+            counted = torch.full((H * W * 3,), -7.0, dtype=torch.float32, device="cuda")
+            counters = torch.zeros(4, dtype=torch.int64, device="cuda")
+            ctx.render_device(counted, counting, counters)
         torch.cuda.synchronize()
     # trace rows count y from the bottom: image row H - 1 - y
     E = c.cpu().numpy().reshape(H, W, nsub * nsub, n, 3)[::-1]
@@ -125,6 +136,10 @@ def check_render_equals_trace(name, W, H, n, nsub, passes):
         mean = np.clip(m1[:, :, j].astype(np.float32), np.float32(0), np.float32(1))
         pix = (mean.astype(np.float64) * float(inv32) + pix.astype(np.float64)).astype(np.float32)
     assert np.array_equal(shot.cpu().numpy().reshape(H, W, 3), pix)
+    if not count:
+        return E, None
+    assert torch.equal(shot, counted)  # the counting kernel's image is the plain one's
+    return E, counters.cpu().tolist()
 
 
 # ---- (b) fast against exact, path by path -------------------------------------

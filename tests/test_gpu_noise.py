@@ -34,6 +34,7 @@ pytestmark = pytest.mark.gpu
 
 import ptgpu  # noqa: E402
 import pyoracle as po  # noqa: E402
+import range_scenes  # noqa: E402
 
 SEED = 0x5EED0001
 EXACT = ptgpu.FLAG_EXACT_MATH
@@ -57,26 +58,37 @@ def _require_gpu():
 
 @functools.lru_cache(maxsize=None)
 def _scene(name, W, H):
+    if name in range_scenes.CASES:  # (tests/test_gpu_radiance_range.py)
+        return range_scenes.make(name, W, H)
     scn = ptgpu.make_scene(name, W, H)
     cam = ptgpu.camera.with_config(scn.camera_parameters)
     return scn, cam
 
 
 @functools.lru_cache(maxsize=None)
-def _paths(name, W, H, n, nsub, seed=SEED):
-    """Radiance of every path from the oracle: float32 [H (image row), W, nsub^2, n, 3], read-only."""
+def _paths_and_segments(name, W, H, n, nsub, seed=SEED):
+    """Every path from the oracle: its radiance, float32 [H (image row), W, nsub^2, n, 3], and its
+    segment count, int64 [H, W, nsub^2, n]; both read-only."""
     scn, cam = _scene(name, W, H)
     sp = np.ascontiguousarray(scn.to_array().view(po.SPHERE_DT))
     ca = np.ascontiguousarray(cam.to_array().view(po.CAMERA_DT))
     E = np.zeros((H, W, nsub * nsub, n, 3), dtype=np.float32)
+    segs = np.zeros((H, W, nsub * nsub, n), dtype=np.int64)
     for y in range(H):  # sample_f32's y counts from the bottom: image row H-1-y
         for x in range(W):
             for sy in range(nsub):
                 for sx in range(nsub):
                     for s in range(n):
-                        E[H - 1 - y, x, sy * nsub + sx, s], _ = po.sample_f32(sp, ca, W, H, nsub, seed, x, y, sx, sy, s)
+                        j = (H - 1 - y, x, sy * nsub + sx, s)
+                        E[j], segs[j] = po.sample_f32(sp, ca, W, H, nsub, seed, x, y, sx, sy, s)
     E.setflags(write=False)
-    return E
+    segs.setflags(write=False)
+    return E, segs
+
+
+def _paths(name, W, H, n, nsub, seed=SEED):
+    """Radiance of every path from the oracle: float32 [H (image row), W, nsub^2, n, 3], read-only."""
+    return _paths_and_segments(name, W, H, n, nsub, seed)[0]
 
 
 def _cl(c):

@@ -51,9 +51,10 @@ def test_reference_f64_matches_mode_a_xs(name, W, H, samps):
     check_matches_mode_a_xs(name, W, H, samps)
 
 
-def check_matches_mode_a_xs(name, W, H, samps, nsub=2):
-    """The module's criterion on one frame (also used by tests/test_gpu_frame_shapes.py)."""
-    scn = ptgpu.make_scene(name, W, H)
+def check_matches_mode_a_xs(name, W, H, samps, nsub=2, scene=None):
+    """The module's criterion on one frame (also used by tests/test_gpu_frame_shapes.py); `scene`:
+    the frame's scene where `name` is not a built-in one.  Returns the two double images."""
+    scn = scene if scene is not None else ptgpu.make_scene(name, W, H)
     cam, sp, ca = _arrays(scn)
     img = np.zeros((H * W, 3))
     ptgpu.render(scn, cam, img, W, H, samps, nsub, SEED, flags=ptgpu.FLAG_REFERENCE_F64)
@@ -71,6 +72,7 @@ def check_matches_mode_a_xs(name, W, H, samps, nsub=2):
         torch.cuda.synchronize()
     assert int(segs.item()) == rsegs
     assert np.array_equal(out.cpu().numpy().reshape(H, W, 3), ref.astype(np.float32))
+    return img.reshape(H, W, 3), ref
 
 
 @pytest.mark.parametrize("name", list(zoo.CASES) + ["box", "simple", "synthetic:300"])
