@@ -116,8 +116,10 @@ typedef struct ptg_params {
 #define PTG_FLAG_COUNT_NONFINITE 2
 /* PTG_FLAG_REFERENCE_F64: render with the reference's own double-precision
  * arithmetic, operation for operation (src/main.cpp:30-197 and the pt
- * library: linear strict-< scan, (-hb -+ sq)/a roots, libm-style
- * sin/cos/pow, sequential r += c/samps) instead of the fp32 megakernel --
+ * library: linear strict-< scan, (-hb -+ sq)/a roots, correctly rounded
+ * sin/cos (csrc/sincos_cr.hpp: glibc's bits on all but 0.15 % of the angles
+ * a draw can give), libm-style pow, sequential r += c/samps) instead of the
+ * fp32 megakernel --
  * a parity mode (csrc/ref64.hpp), several times slower.  Only the counter-RNG
  * draws differ from the reference (as in every mode).  ptg_render keeps the
  * doubles; ptg_render_device rounds them into its float slab.  Not for
@@ -165,6 +167,9 @@ typedef struct ptg_params {
  *        if cs > 0: a shadow segment, an ordinary nearest-hit scan from p
  *        along l (counted like any scan); if its winner is light k:
  *        E += T * Le_k * (cs 2 omc L)
+ *        (the scan's tie rule holds here too: a listed light with a sphere of
+ *        equal geometry at a lower scene index is occluded by it everywhere
+ *        and adds nothing, as it is never seen without the flag)
  *   4. the path's next hit skips the emission of a sphere on the light list
  *      when it meets that sphere on its FRONT face (that one hit only; also
  *      when step 3 added nothing).  A listed sphere met from inside (back
@@ -763,7 +768,14 @@ int ptg_tonemap_device(const float *d_image, uint8_t *d_out, size_t count, void 
  * anchor axis chosen for a huge sphere (0..2; -1 = camera-facing anchor, or
  * not huge) and the order of the linear scan (scan_order[j] = scene index of
  * the sphere tested j-th; scenes of <= 64 spheres).  Exact ties between
- * candidate roots go to the sphere tested first. */
+ * candidate roots (two spheres of equal geometry: one pasted twice, a lamp's
+ * shell on a body of the same radius) go to the sphere tested first: the
+ * spheres of one kind are tested in scene index order, so among equal spheres
+ * that is the lowest scene index.  Scenes of more than 64 spheres (BVH):
+ * every root is divided and the smallest t wins, the lowest scene index on
+ * exact ties -- whatever order the walk visits the spheres in, so the frame
+ * does not depend on the order of the scene's spheres beyond the order inside
+ * each group of equal spheres.  The sphere that loses a tie is never seen. */
 int ptg_scene_layout(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, int32_t *anchor_axis,
                      int32_t *scan_order);
 

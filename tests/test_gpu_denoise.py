@@ -10,6 +10,7 @@ import pytest
 
 import denoise_ref
 import ptgpu
+import tie_scenes
 from denoise_camera import OFF_AXIS
 from ptgpu.scene import _sub, length
 
@@ -22,6 +23,8 @@ DEV = "cuda:0"
 
 
 def scene_and_camera(name, W, H):
+    if name in tie_scenes.CASES:  # (tests/test_gpu_ties.py)
+        return tie_scenes.make(name, W, H)
     scn = ptgpu.make_scene(name, W, H)
     if name.startswith("box"):
         c = scn.camera_parameters
@@ -109,6 +112,9 @@ def test_filter_iterations_0_copies(frames):
 FEATURE_CASES = [("box", 64, 48, 1), ("box", 64, 48, 2), ("simple", 64, 48, 1), ("simple", 64, 48, 2),
                  ("box_mirror", 64, 48, 1), ("box_mirror", 64, 48, 2), ("synthetic:300", 32, 18, 1),
                  ("synthetic:300", 32, 18, 2)]
+# scenes with exact ties (tests/tie_scenes.py): the albedo is the tie's winner -- the sphere visited first,
+# lowest scene index -- which the restatement's strict < in index order gives as well
+FEATURE_CASES += [(name, 64, 48, nsub) for name in ("twins_lin_low", "twins_bvh_low", "stack9_b") for nsub in (1, 2)]
 
 
 def _features(scn, cam, p):

@@ -38,6 +38,14 @@ Measured on an MI355X (S = 2: open_014's one path against y = 0):
     synthetic:300    0       0          2
     cluster64        0       0          2
     cluster65        0       0          2
+    twins_lin_low    0       0          2
+    twins_room_low  17      14         53
+    twins_bvh_low    0       0          2
+    stack9_a         0       0          2
+
+(The last four hold exact ties, tests/tie_scenes.py: the fast mode gives a tie
+to the same sphere as the exact mode.  S stays 2: every bound is at least
+twice its measured count.)
 """
 import functools
 
@@ -51,6 +59,7 @@ import ptgpu  # noqa: E402
 import pyoracle as po  # noqa: E402
 import range_scenes  # noqa: E402
 import shape_scenes as ss  # noqa: E402
+import tie_scenes  # noqa: E402
 from test_gpu_noise import _accumulate, _quant, _read, _sums  # noqa: E402
 from test_wall_rules import sunk_scene  # noqa: E402
 
@@ -69,6 +78,8 @@ def _scene(name, W, H):
         return ss.make(name, W, H)
     if name in range_scenes.CASES:  # (tests/test_gpu_radiance_range.py)
         return range_scenes.make(name, W, H)
+    if name in tie_scenes.CASES:  # (tests/test_gpu_ties.py)
+        return tie_scenes.make(name, W, H)
     scn = sunk_scene(W, H) if name == "sunk_scene" else ptgpu.make_scene(name, W, H)
     return scn, ptgpu.camera.with_config(scn.camera_parameters)
 
@@ -147,7 +158,7 @@ N_PATHS = 4096
 TW, TH = 160, 120
 S_SLACK = 2  # the table above; it may not exceed 20 (0.5 % of the paths)
 SCENES_B = ["box", "box_mirror", "simple", "room4", "room16", "room59", "sunk_scene", "open_014", "sliver",
-            "synthetic:300", "cluster64", "cluster65"]
+            "synthetic:300", "cluster64", "cluster65", "twins_lin_low", "twins_room_low", "twins_bvh_low", "stack9_a"]
 
 
 def _coords():

@@ -45,6 +45,7 @@ import light_ref  # noqa: E402
 import light_zoo as zoo  # noqa: E402
 import ptgpu  # noqa: E402
 import test_oracle_light_sampling as oracle_ls  # noqa: E402
+import tie_scenes  # noqa: E402
 from test_gpu_statistical import two_sample_check  # noqa: E402
 
 SEED = 0x5EED0001
@@ -64,6 +65,8 @@ def _scene(name, W, H):
     if name.startswith("zoo:"):  # (built for 32x24; other sizes keep that aspect ratio)
         assert W * zoo.H == H * zoo.W
         scn = zoo.CASES[name[4:]]()
+    elif name in tie_scenes.LAMPS:  # (tests/test_gpu_ties.py: `three` with a dark twin of each light)
+        scn = tie_scenes.make(name, W, H)[0]
     else:
         scn = ptgpu.make_scene(name, W, H)
     return scn, ptgpu.camera.with_config(scn.camera_parameters)
@@ -195,7 +198,8 @@ def _f64_frame(name, W, H, n):
 
 @MODES
 @pytest.mark.parametrize("name,W,H,n", [("box", 64, 48, 64), ("simple", 64, 48, 64), ("synthetic:300", 32, 18, 128)]
-                         + [(f"zoo:{k}", zoo.W, zoo.H, 64) for k in zoo.CASES])
+                         + [(f"zoo:{k}", zoo.W, zoo.H, 64) for k in zoo.CASES]
+                         + [(k, zoo.W, zoo.H, 64) for k in tie_scenes.LAMPS])
 def test_fp32_against_the_double_definition(name, W, H, n, mode):
     _require_gpu()
     ref = _f64_frame(name, W, H, n).astype(np.float64)
@@ -271,7 +275,8 @@ def _quant(c):
 @MODES
 @pytest.mark.parametrize("name,W,H,n", [("box", 16, 12, 4), ("synthetic:300", 16, 9, 2)]
                          + [(f"zoo:{k}", 16, 12, 2) for k in ("three", "sixteen", "glass_lamp", "permuted",
-                                                              "bvh_lights")])
+                                                              "bvh_lights")]
+                         + [(k, 16, 12, 2) for k in tie_scenes.LAMPS])
 def test_pool_kernel_equals_the_trace_kernel(name, W, H, n, mode):
     _require_gpu()
     nsub = 2

@@ -5,8 +5,11 @@ Mode A/xs restates src/main.cpp:30-197 and the pt library line by line in
 double (no FMA, libm), with the counter-RNG draws; ref64.hpp is the same
 restatement on the GPU, one lane per sub-pixel running its samples in order.
 Division and square root are correctly rounded on both sides, the only
-possible per-operation differences are the last ulp of sin/cos/pow (device
-math library vs glibc).  So the images agree to rounding level: the bar here
+possible per-operation differences are the last ulp of sin/cos/pow: the
+device's sin / cos are csrc/sincos_cr.hpp's, correctly rounded
+(tests/test_sincos_cr.py), which glibc's are on all but 0.15 % of the angles
+a draw can give; pow is the device math library's and only feeds a compare.
+So the images agree to rounding level: the bar here
 is max |diff| <= 1e-9 on the double image (the reference's own image
 precision is ~1e-16; an ulp difference amplified through a chaotic path
 would show as a much larger jump), plus the segment counts exactly.
