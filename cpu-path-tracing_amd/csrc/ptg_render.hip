@@ -1534,9 +1534,18 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         recs = lds_lin;
     }
     __shared__ float4 lds_cam[4];
+    // a starting path's T, depth and E, read in paths_done (linear kernel: 2
+    // LDS reads and a move for 7 moves, box -0.9 %; the BVH kernel, bound by
+    // its node loads, keeps the moves: C5 +0.3 % with the reads)
+    constexpr bool kStartLds = !kBvh;
+    __shared__ float4 lds_start[kStartLds ? 2 : 1];
     __shared__ int lds_coop_done;  // cooperative levels: waves of the workgroup finished
     if (threadIdx.x == 0) {
         lds_coop_done = 0;
+        if constexpr (kStartLds) {
+            lds_start[0] = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(0));
+            lds_start[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
         const CamC c = cam_of(A);
         lds_cam[0] = c.p;
         lds_cam[1] = c.b;
@@ -1634,7 +1643,6 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 
-    int item = lane < total ? lane : -1;
     int slot = 0;
     f3 o, d, T, E;
     int depth = 0;
@@ -1704,7 +1712,6 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     // (BVH scenes: a started ray is fresh -- in neither of the main loop's
     // scan-phase masks, which its lane has left by then)
     auto begin = [&](int it, f3 ro, f3 rd, uint32_t rs) {
-        item = it;
         if (nv == 64) {
             slot = it & 63;
         } else {
@@ -1731,8 +1738,12 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     // the bools lived in VGPRs and every iteration re-formed their lane masks
     // with compares.  hmask: a prefetched ray in LDS; wmask: path ended, no
     // prefetched ray yet (E kept until the batch); pmask: a finished path's
-    // radiance parked in the lane's LDS record
+    // radiance parked in the lane's LDS record; amask: the lane holds a path
+    // (the scalar unit sets it at unit start, clears a bit where a path ends
+    // with no prefetched ray to start, sets it where refill starts an idle
+    // lane; a lane in wmask is not in amask)
     unsigned long long hmask = 0ull, wmask = 0ull, pmask = 0ull;
+    unsigned long long amask = __ballot(lane < total);
     auto lane_in = [](unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); };
     // light sampling: the lane's shadow-segment state and its two masks (a
     // path that ends leaves both bits clear, so a started path begins clear)
@@ -1748,11 +1759,11 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         }
         return io;
     };
-    if (item >= 0) {
+    if (lane < total) {
         f3 ro, rd;
         uint32_t rs;
-        ray_of(item, ro, rd, rs);
-        begin(item, ro, rd, rs);
+        ray_of(lane, ro, rd, rs);
+        begin(lane, ro, rd, rs);
     }
     if (64 + lane < total) {
         f3 ro, rd;
@@ -1793,18 +1804,40 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         if (done == 0ull)
             return;
         const unsigned long long start = done & hmask;
-        if (lane_in(done)) {
-            item = -1;
-            if (lane_in(start)) {
-                const float4 *rec = pre_rec();
-                const float4 p0 = rec[0], p1 = rec[1];
-                park();
+        if (lane_in(start)) {
+            const float4 *rec = pre_rec();
+            const float4 p0 = rec[0], p1 = rec[1];
+            park();
+            if constexpr (kStartLds) {
+                // T, depth and E read from the workgroup's constant record
+                // (uniform address; the offset is opaque so the reads stay
+                // here), issued behind the ray's reads and the park: one
+                // wait for all of them, and the values land in the
+                // loop-carried registers without copies
+                unsigned so = 0;  // (a byte offset: no shift to scale an index)
+                asm volatile("" : "+v"(so));
+                const float4 *sc = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(lds_start) + so);
+                const float4 c0 = sc[0], c1 = sc[1];
+                if (nv == 64) {
+                    slot = __float_as_int(p1.z) & 63;
+                } else {
+                    int q;
+                    divmod_nv(__float_as_int(p1.z), q, slot);
+                }
+                o = mk3(p0.x, p0.y, p1.w);
+                d = mk3(p0.z, p0.w, p1.x);
+                st = __float_as_uint(p1.y);
+                T = mk3(c0.x, c0.y, c0.z);
+                depth = __float_as_int(c0.w);
+                E = mk3(c1.x, c1.y, c1.z);
+            } else {
                 begin(__float_as_int(p1.z), mk3(p0.x, p0.y, p1.w), mk3(p0.z, p0.w, p1.x), __float_as_uint(p1.y));
             }
         }
         pmask |= start;
         hmask &= ~start;
         wmask |= done & ~start;
+        amask &= ~done | start;
     };
     // refill batch: flush parked paths, prefetch camera rays for lanes
     // without one, start idle lanes
@@ -1817,7 +1850,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
 #if PTG_BLOCK_STATS == 3
                 PTG_SUB_T(rf_t0);
 #endif
-                const unsigned long long idle = wmask | __ballot(item < 0);
+                const unsigned long long idle = ~amask;  // (waiting lanes included)
                 if (lane_in(pmask))
                     flush_parked();
                 if (lane_in(wmask))
@@ -1848,6 +1881,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
                         store_pre(ni, ro, rd, rs);
                 }
                 hmask |= got & ~idle;
+                amask |= got & idle;
                 next += nn;
 #if PTG_BLOCK_STATS == 3
                 {
@@ -1878,27 +1912,27 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         };
 #endif
         for (;;) {
-            if ((__ballot(item >= 0) | wmask) == 0ull)
+            if ((amask | wmask) == 0ull)
                 break;
             PTG_STAT(0);
 #if PTG_BLOCK_STATS == 3
             lin_phase(5);
             float t3 = 0.0f;
             const LinRec *w3 = nullptr;
-            if (item >= 0) {
+            if (lane_in(amask)) {
                 if constexpr (kCount)
                     segs += 1;
                 w3 = scene_scan<kExact, kCount>(A, recs, o, d, t3, scnt);
             }
             lin_phase(0);
-            paths_done(__ballot(item >= 0 && shade<kExact>(w3 != recs + A.n ? &w3->s : nullptr, t3, trig, o, d, T, E, depth, st)));
+            paths_done(__ballot(lane_in(amask) && shade<kExact>(w3 != recs + A.n ? &w3->s : nullptr, t3, trig, o, d, T, E, depth, st)));
             lin_phase(3);
             refill();
             lin_phase(4);
 #else
             bool done = false;
             [[maybe_unused]] LsIo io = ls_io();
-            if (item >= 0) {
+            if (lane_in(amask)) {
                 PTG_STAT(1);
                 if constexpr (kCount)
                     segs += 1;
@@ -1943,7 +1977,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         unsigned long long ph_cyc[6] = {0, 0, 0, 0, 0, 0}, ph_t = clock64();
 #endif
         for (;;) {
-            if ((__ballot(item >= 0) | wmask) == 0ull)
+            if ((amask | wmask) == 0ull)
                 break;
             PTG_PHASE(5);
             // the lanes' scan phase as wave masks (like hmask / wmask / pmask):
@@ -1951,7 +1985,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
             // and in neither.  A lane's scan is done when ni == -1 and no leaf
             // is parked: two single-compare ballots (a ballot of the combined
             // predicate is materialised as v_cndmask + v_cmp)
-            const unsigned long long act = __ballot(item >= 0);
+            const unsigned long long act = amask;
             {
                 const unsigned long long fresh = act & ~(wk | rd);
                 if (lane_in(fresh)) {
@@ -1977,7 +2011,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
                     for (;;) {
                         // ballots of single compares: a ballot of a combined
                         // predicate (x && y) is materialised as v_cndmask + v_cmp,
-                        // 2 VALU each.  A walking lane has item >= 0 (an item
+                        // 2 VALU each.  A walking lane is in amask (a path
                         // ends only in shading, after the walk), and na does not
                         // change inside the walk.
                         const unsigned long long mt = wk;
