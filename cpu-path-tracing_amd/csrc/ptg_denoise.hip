@@ -283,9 +283,11 @@ int ptg_denoise_host(const float *color, const float *var, const float *feat, in
 
 // Host helper: the feature frame of ptg_features_device, width * height * 12 floats in ptg_render's row
 // order, copied to the host (shard_count 1).  Synchronous.
-int ptg_features(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
-                 int device, float *features)
+static int features_host(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
+                         int device, int32_t max_bounces, float *features)
 {
+    if (max_bounces < -1 || max_bounces > PTG_MAX_FOLLOW_BOUNCES)  // (-1: ptg_features)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: max_bounces must be 0..16");
     if (!features || !params || !cam)
         return fail(PTG_ERR_INVALID_ARGUMENT, "features: NULL output, camera or params");
     if (params->width <= 0 || params->height <= 0)
@@ -303,7 +305,8 @@ int ptg_features(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *
     if (!rc && hipMalloc(&d_feat, (size_t)rows * params->width * kFeat * sizeof(float)) != hipSuccess)
         rc = fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the feature slab failed");
     if (!rc)
-        rc = ptg_features_device(ctx, params, d_feat, nullptr);
+        rc = max_bounces < 0 ? ptg_features_device(ctx, params, d_feat, nullptr)
+                             : ptg_features_follow_device(ctx, params, max_bounces, d_feat, nullptr);
     if (!rc) {
         const hipError_t e = hipMemcpy(features, d_feat, frame * sizeof(float), hipMemcpyDeviceToHost);
         if (e != hipSuccess)
@@ -313,6 +316,20 @@ int ptg_features(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *
         (void)hipFree(d_feat);
     ptg_context_destroy(ctx);
     return rc;
+}
+
+int ptg_features(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
+                 int device, float *features)
+{
+    return features_host(spheres, n_spheres, cam, params, device, -1, features);
+}
+
+int ptg_features_follow(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                        const ptg_params *params, int device, int32_t max_bounces, float *features)
+{
+    if (max_bounces < 0)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: max_bounces must be 0..16");
+    return features_host(spheres, n_spheres, cam, params, device, max_bounces, features);
 }
 
 // internal (the drivers here and in csrc/ptg_multi.cpp): the filter's parameters a driver runs with -- `denoise`,
@@ -331,7 +348,18 @@ int ptg_denoise_params_for_(const ptg_camera *cam, int32_t width, int32_t height
         return rc;
     if (const char *why = params_error(out))
         return fail(PTG_ERR_INVALID_ARGUMENT, why);
+    if (out->follow_bounces < 0 || out->follow_bounces > PTG_MAX_FOLLOW_BOUNCES)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "denoise: follow_bounces must be 0..16");
     return PTG_OK;
+}
+
+// internal (the same drivers): the feature slab a driver's filter is guided by -- the first hit, or with
+// follow_bounces 1..16 the first diffuse hit behind mirrors and glass
+int ptg_features_for_(ptg_context *ctx, const ptg_params *params, const ptg_denoise_params *k, float *d_feat,
+                      void *stream)
+{
+    return k->follow_bounces ? ptg_features_follow_device(ctx, params, k->follow_bounces, d_feat, stream)
+                             : ptg_features_device(ctx, params, d_feat, stream);
 }
 
 }  // extern "C"
@@ -429,7 +457,7 @@ int render_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camer
         }
         if ((r = ptg_resolve_device(ctx, &p, done, d_color, nullptr)) ||
             (r = ptg_noise_device(ctx, &p, done, 0.0, 1.0, d_var, nullptr, nullptr, nullptr)) ||
-            (r = ptg_features_device(ctx, &p, d_feat, nullptr)) ||
+            (r = ptg_features_for_(ctx, &p, &k, d_feat, nullptr)) ||
             (r = ptg_denoise_device(d_color, d_var, d_feat, W, H, &k, d_out, nullptr, d_scratch, scratch_bytes,
                                     nullptr)))
             return r;
@@ -548,7 +576,7 @@ int render_adaptive_denoised(const ptg_sphere *spheres, size_t n_spheres, const 
         }
         if ((r = ptg_resolve_active_device(ctx, &p, d_color, nullptr)) ||
             (r = ptg_noise_active_device(ctx, &p, 1.0, d_var, nullptr, nullptr)) ||
-            (r = ptg_features_device(ctx, &p, d_feat, nullptr)) ||
+            (r = ptg_features_for_(ctx, &p, &k, d_feat, nullptr)) ||
             (r = ptg_denoise_device(d_color, d_var, d_feat, W, H, &k, d_out, nullptr, d_scratch, scratch_bytes,
                                     nullptr)))
             return r;

@@ -37,6 +37,8 @@ extern "C" int ptg_set_error_(int code, const char *msg);
 // defaults; the camera's pixel_spread where none is given), checked
 extern "C" int ptg_denoise_params_for_(const ptg_camera *cam, int32_t width, int32_t height,
                                        const ptg_denoise_params *denoise, ptg_denoise_params *out);
+extern "C" int ptg_features_for_(ptg_context *ctx, const ptg_params *params, const ptg_denoise_params *k,
+                                 float *d_feat, void *stream);
 
 namespace {
 
@@ -798,7 +800,7 @@ int multi_resolve_filtered(ptg_multi *m, const ptg_params *p, int32_t samples_do
     if ((rc = gather_unshard_device(m, p, slab_elems)) || (rc = gather_unshard_device(m, p, slab_elems, /*variance=*/true)))
         return rc;
     Shard &root = m->shards[0];
-    if ((rc = ptg_features_device(root.ctx, p, m->feat, root.stream)))  // p: shard_count 1 (check_frame_params)
+    if ((rc = ptg_features_for_(root.ctx, p, &k, m->feat, root.stream)))  // p: shard_count 1 (check_frame_params)
         return rc;
     MULTI_HIP(hipSetDevice(root.id));
     if ((rc = ptg_denoise_device(m->image, m->var_image, m->feat, p->width, p->height, &k, m->filtered, nullptr,

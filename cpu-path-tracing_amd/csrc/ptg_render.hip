@@ -2848,6 +2848,8 @@ __global__ __launch_bounds__(256) void features_kernel(KArgs A, float4 *__restri
     out[2] = hits > 0 ? make_float4(a.x / k, a.y / k, a.z / k, 0.0f) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
 }
 
+#include "follow_features.hpp"  // features_follow_kernel (ptg_features_follow_device)
+
 // ptg_math_probe_device: the primitives as the render kernels call them
 template <bool kExact>
 __global__ __launch_bounds__(256) void math_probe_kernel(int op, const float *in, float *out, int n,
@@ -3968,6 +3970,38 @@ int ptg_features_device(ptg_context *ctx, const ptg_params *params, float *d_fea
         features_kernel<true><<<blocks, 256, 0, s>>>(A, reinterpret_cast<float4 *>(d_feat));
     else
         features_kernel<false><<<blocks, 256, 0, s>>>(A, reinterpret_cast<float4 *>(d_feat));
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_features_follow_device(ptg_context *ctx, const ptg_params *params, int32_t max_bounces, float *d_feat,
+                               void *stream)
+{
+    if (max_bounces < 0 || max_bounces > PTG_MAX_FOLLOW_BOUNCES)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: max_bounces must be 0..16");
+    if (!ctx || !d_feat)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: NULL context or output");
+    if (reinterpret_cast<uintptr_t>(d_feat) % 16)
+        return fail(PTG_ERR_INVALID_ARGUMENT, "features: the output must be 16-byte aligned");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    int grid = 0;
+    // the frame's geometry only, as ptg_features_device plans it
+    ptg_params geo = *params;
+    geo.samples = 1;
+    geo.chunk_samples = 0;
+    geo.flags = PTG_FLAG_EXACT_MATH;
+    if ((rc = begin_launch(ctx, &geo, A, grid, s, /*with_acc=*/false)))
+        return rc;
+    const long long pixels = (long long)A.slab_rows * A.W;
+    const unsigned blocks = (unsigned)((pixels + 255) / 256);
+    if (A.n > kLinearMax)
+        features_follow_kernel<true><<<blocks, 256, 0, s>>>(A, max_bounces, reinterpret_cast<float4 *>(d_feat));
+    else
+        features_follow_kernel<false><<<blocks, 256, 0, s>>>(A, max_bounces, reinterpret_cast<float4 *>(d_feat));
     PTG_HIP(hipGetLastError());
     return PTG_OK;
 }

@@ -9,7 +9,8 @@
 //                 [--light-sampling]
 //                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]
 //                  [--adaptive [--dilate D] [--spp-map FILE]]]
-//                 [--denoise | --filter [--denoise-iterations N]] [--features-out PREFIX]
+//                 [--denoise | --filter [--denoise-iterations N] [--denoise-follow N]]
+//                 [--features-out PREFIX [--features-follow N]]
 //
 //   spp      total samples per pixel (main.cpp:206: divided by the 4 sub-pixels), default 4
 //   scene    box_mirror (the reference binary's scene, main.cpp:25,208) | box | simple |
@@ -59,6 +60,11 @@
 //            for bit for any device list; alone on one device it is --denoise's.  Takes
 //            --denoise-iterations, needs --spp >= 8, and does not combine with --denoise (exit
 //            status 2).
+//   --denoise-follow N  with --denoise or --filter (exit status 2 without): the filter's guide
+//            follows each ray through at most N (0..16) mirror and glass surfaces to the first
+//            diffuse one (ptg_denoise_params.follow_bounces; 0, the default: the first hit).
+//   --features-follow N  with --features-out: the same for the features written
+//            (ptg_features_follow).
 //   --features-out PREFIX  the first-hit features of every pixel (ptg_features; no RNG, the
 //            sub-pixel centres): PREFIX_normal.ppm (P6, round((n + 1) / 2 * 255) per axis, the
 //            mean facing normal; sky 0 0 0 -> 128 128 128), PREFIX_albedo.ppm (P6, round(a * 255),
@@ -188,6 +194,7 @@ int main(int argc, char *argv[])
     std::string spp_map;
     bool denoise = false, filter = false;
     int denoise_iterations = -1;  // -1: the default
+    int denoise_follow = -1, features_follow = -1;  // -1: not given (the first hit)
     std::string features_out;
     ptg_noise_target target{};
     target.floor = 0.01;
@@ -259,6 +266,10 @@ int main(int argc, char *argv[])
                 filter = true;
             else if (a == "--denoise-iterations")
                 denoise_iterations = std::atoi(val().c_str());
+            else if (a == "--denoise-follow")
+                denoise_follow = std::atoi(val().c_str());
+            else if (a == "--features-follow")
+                features_follow = std::atoi(val().c_str());
             else if (a == "--features-out")
                 features_out = val();
             else {
@@ -278,6 +289,15 @@ int main(int argc, char *argv[])
     int const samps = spp / (num_subpixels * num_subpixels);
     if (denoise_iterations != -1 && ((!denoise && !filter) || denoise_iterations < 0 || denoise_iterations > 8)) {
         std::fprintf(stderr, "--denoise-iterations needs --denoise or --filter and a value in 0..8\n");
+        return 2;
+    }
+    if (denoise_follow != -1 && ((!denoise && !filter) || denoise_follow < 0 || denoise_follow > PTG_MAX_FOLLOW_BOUNCES)) {
+        std::fprintf(stderr, "--denoise-follow needs --denoise or --filter and a value in 0..16\n");
+        return 2;
+    }
+    if (features_follow != -1 &&
+        (features_out.empty() || features_follow < 0 || features_follow > PTG_MAX_FOLLOW_BOUNCES)) {
+        std::fprintf(stderr, "--features-follow needs --features-out and a value in 0..16\n");
         return 2;
     }
     if (denoise && filter) {
@@ -321,7 +341,8 @@ int main(int argc, char *argv[])
     if (!features_out.empty()) {
         std::vector<float> feat;
         int const frc = nd < 1 ? PTG_ERR_INVALID_ARGUMENT
-                               : pt::gpu::feature_frame(some_scene, cam, feat, width, height, num_subpixels, devs[0]);
+                               : pt::gpu::feature_frame(some_scene, cam, feat, width, height, num_subpixels, devs[0],
+                                                        features_follow < 0 ? 0 : features_follow);
         if (frc != PTG_OK) {
             std::fprintf(stderr, "features failed (%d): %s\n", frc, ptg_last_error());
             return 1;
@@ -337,6 +358,8 @@ int main(int argc, char *argv[])
     dn.pixel_spread = 0.0f;
     if (denoise_iterations >= 0)
         dn.iterations = denoise_iterations;
+    if (denoise_follow >= 0)
+        dn.follow_bounces = denoise_follow;
     if (to_noise) {  // render until converged: --spp is the most it takes
         if (nd < 1) {
             std::fprintf(stderr, "--devices needs at least one device\n");

@@ -308,8 +308,11 @@ inline int render_image_adaptive_denoised(scene const &scn, camera const &cam, s
 
 // The first-hit feature frame (ptg_features): width * height * 12 floats in the
 // image's row order, {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0} per pixel.
+// follow_bounces 1..16: ptg_features_follow, the first diffuse hit behind
+// mirrors and glass, the last word the mean number of bounces.  (The denoised
+// drivers above take the same choice as denoise->follow_bounces.)
 inline int feature_frame(scene const &scn, camera const &cam, std::vector<float> &features, int width, int height,
-                         int num_subpixels = 2, int device = -1)
+                         int num_subpixels = 2, int device = -1, int follow_bounces = 0)
 {
     features.assign(static_cast<std::size_t>(width) * static_cast<std::size_t>(height) * 12, 0.0f);
     ptg_params p{};
@@ -321,6 +324,10 @@ inline int feature_frame(scene const &scn, camera const &cam, std::vector<float>
     p.band_rows = 1;
     p.shard_rank = 0;
     p.shard_count = 1;
+    if (follow_bounces)
+        return ptg_features_follow(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
+                                   reinterpret_cast<ptg_camera const *>(&cam), &p, device, follow_bounces,
+                                   features.data());
     return ptg_features(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
                         reinterpret_cast<ptg_camera const *>(&cam), &p, device, features.data());
 }

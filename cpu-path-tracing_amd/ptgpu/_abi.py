@@ -37,6 +37,7 @@ EXPORTS = (
     "ptg_multi_resolve_denoised", "ptg_multi_resolve_active_denoised", "ptg_multi_render_denoised",
     "ptg_multi_render_to_noise_denoised", "ptg_multi_render_adaptive_denoised", "ptg_render_denoised_multi",
     "ptg_render_to_noise_denoised_multi", "ptg_render_adaptive_denoised_multi",
+    "ptg_features_follow_device", "ptg_features_follow",
 )
 
 
@@ -88,7 +89,7 @@ assert C.sizeof(AdaptiveTarget) == 32 and C.sizeof(AdaptiveReport) == 88 + 20 * 
 
 
 class DenoiseParams(C.Structure):  # ptg_denoise_params
-    _fields_ = [("iterations", C.c_int32), ("reserved0_", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float),
+    _fields_ = [("iterations", C.c_int32), ("follow_bounces", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float),
                 ("k_plane", C.c_float), ("k_albedo", C.c_float), ("eps_color", C.c_float),
                 ("pixel_spread", C.c_float), ("reserved_", C.c_float * 8)]
 
@@ -177,6 +178,8 @@ def lib():
             "ptg_render_to_noise_denoised": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(NoiseTarget),
                                                  C.POINTER(DenoiseParams), P, C.POINTER(NoiseReport)]),
             "ptg_features": (I, [P, C.c_size_t, P, C.POINTER(Params), I, P]),
+            "ptg_features_follow_device": (I, [P, C.POINTER(Params), C.c_int32, P, P]),
+            "ptg_features_follow": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.c_int32, P]),
             "ptg_noise_active_device": (I, [P, C.POINTER(Params), C.c_double, P, P, P]),
             "ptg_render_adaptive_denoised": (I, [P, C.c_size_t, P, C.POINTER(Params), I, C.POINTER(AdaptiveTarget),
                                                  C.POINTER(DenoiseParams), P, P, C.POINTER(AdaptiveReport)]),

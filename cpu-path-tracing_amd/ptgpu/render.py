@@ -449,7 +449,8 @@ class MultiContext:
         return (out, counts) if sample_counts else out
 
 
-# every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel)
+# every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel) and
+# follow_features.hpp (the followed-feature kernel): neither holds a timed kernel
 KERNEL_SOURCES = ("ptg_render.hip", "pt_device.hpp", "bvh_build.hpp", "kernel_args.hpp", "scene_prep.hpp",
                   "launch_plan.hpp", "ptg_error.hpp")
 
@@ -741,17 +742,26 @@ class Context:
                                             C.c_void_p(self._stream(stream))), "ptg_noise_active_device")
 
     # ---- denoising (ptg_features_device; the filter itself needs no context: denoise())
-    def features(self, params: Params, out=None, stream=None):
+    def features(self, params: Params, out=None, stream=None, *, follow_bounces: Optional[int] = None):
         """The first-hit features of every slab pixel (float32, slab rows*W*12:
         {n.xyz, z}, {P.xyz, hit}, {albedo.rgb, 0}), the guide of denoise().
         Deterministic camera rays through the renderer's exact scan: no
         dependence on seed, samples or flags.  Returns `out` ([rows, W, 12]
-        when allocated here)."""
+        when allocated here).  follow_bounces (keyword; None or 0..16):
+        ptg_features_follow_device -- each ray followed through at most that
+        many mirror and glass surfaces to the first diffuse one, word 11 the
+        mean number of bounces; None is ptg_features_device, which 0 equals
+        bit for bit."""
         import torch
         rows = shard_rows(params.height, params.band_rows, params.shard_count)
         if out is None:
             out = torch.zeros((rows, params.width, 12), dtype=torch.float32, device=torch.device("cuda", self.device))
         self._check(out, torch.float32, rows * params.width * 12)
+        if follow_bounces is not None:
+            check(lib().ptg_features_follow_device(self._h, C.byref(params), int(follow_bounces),
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(stream))),
+                  "ptg_features_follow_device")
+            return out
         check(lib().ptg_features_device(self._h, C.byref(params), C.c_void_p(out.data_ptr()),
                                         C.c_void_p(self._stream(stream))), "ptg_features_device")
         return out
@@ -952,13 +962,20 @@ def render_adaptive_denoised(scn, cam, image: np.ndarray, width: int, height: in
     return (out, counts) if sample_counts else out
 
 
-def features(scn, cam, width: int, height: int, num_subpixels: int = 2, device: int = -1) -> np.ndarray:
+def features(scn, cam, width: int, height: int, num_subpixels: int = 2, device: int = -1,
+             follow_bounces: int = 0) -> np.ndarray:
     """ptg_features: the first-hit feature frame on the host, float32
-    [height, width, 12] in render()'s row order."""
+    [height, width, 12] in render()'s row order.  follow_bounces 1..16:
+    ptg_features_follow, the first diffuse hit behind mirrors and glass."""
     sp = _spheres_array(scn)
     ca = _camera_array(cam)
     out = np.zeros((height, width, 12), dtype=np.float32)
     p = make_params(width, height, 1, num_subpixels)
+    if follow_bounces:
+        check(lib().ptg_features_follow(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p),
+                                        C.byref(p), int(device), int(follow_bounces),
+                                        out.ctypes.data_as(C.c_void_p)), "ptg_features_follow")
+        return out
     check(lib().ptg_features(sp.ctypes.data_as(C.c_void_p), len(sp), ca.ctypes.data_as(C.c_void_p), C.byref(p),
                              int(device), out.ctypes.data_as(C.c_void_p)), "ptg_features")
     return out

@@ -589,9 +589,40 @@ int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const
  * (PTG_ERR_INVALID_ARGUMENT otherwise).  Asynchronous on stream. */
 int ptg_features_device(ptg_context *ctx, const ptg_params *params, float *d_feat, void *stream);
 
+/* The same slab (layout, alignment rule, shard handling, rows past the image
+ * untouched, the frame planned as an exact-mode frame), with each ray followed
+ * through mirrors and glass to the first diffuse surface.  A mirror's fuzz draw
+ * is multiplied by 0 and a refraction direction is deterministic, so no draw is
+ * taken.  max_bounces is 0..PTG_MAX_FOLLOW_BOUNCES (PTG_ERR_INVALID_ARGUMENT
+ * outside).  Per ray, with T = (1, 1, 1), b = 0 and the pixel's running z:
+ *   scan (the renderer's exact scan): a miss makes the ray sky whatever b is,
+ *     and it adds nothing to any sum; a hit at t gives p = fma(d, t, o), the
+ *     outward normal on, front = on.d < 0 and the facing normal nn as the
+ *     exact shading forms them, and z' = fma(t, sqrt(d.d), z') for every
+ *     segment of the ray, starting from the pixel's z (a ray that ends in the
+ *     sky leaves the pixel's z as it was);
+ *   stop when the sphere is diffuse or b == max_bounces: n += nn, P += p,
+ *     albedo += T * colour, bounce sum += b, hits += 1 (a ray out of bounces
+ *     on a mirror reports that mirror);
+ *   else follow: T = T * colour, o = p, b += 1, and d by the exact shading's
+ *     arithmetic -- specular: d - 2 (on.d) on; dielectric: v1 = d rsqrt(d.d),
+ *     cth = min(1, -v1.nn), s2 = sqrt0(1 - cth^2), ratio = front ? 0.5 : 2; with
+ *     ratio s2 > 1 (total internal reflection) the mirror formula, else
+ *     perp = (nn cth + v1) ratio, d = perp - nn sqrt(|1 - perp.perp|).  There is
+ *     no Fresnel reflection branch.  Directions stay un-normalised where the
+ *     renderer leaves them so.
+ * Per pixel the 12 floats keep their places: means over the stopping rays,
+ * hit their share of the rays, albedo (1, 1, 1) for a sky pixel, and word 11
+ * (0 in ptg_features_device) the mean b of the stopping rays;
+ * ptg_denoise_device does not read word 11.  With max_bounces = 0 the slab
+ * equals ptg_features_device's bit for bit. */
+#define PTG_MAX_FOLLOW_BOUNCES 16
+int ptg_features_follow_device(ptg_context *ctx, const ptg_params *params, int32_t max_bounces, float *d_feat,
+                               void *stream);
+
 typedef struct ptg_denoise_params {
     int32_t iterations;  /* 0..8 (0 copies the input); iteration i has step 1 << i */
-    int32_t reserved0_;
+    int32_t follow_bounces;  /* the drivers' guide: 0 ptg_features_device, 1..16 ptg_features_follow_device */
     float k_color;       /* weight of |c_p - c_q|^2 / (Vbar_p + Vbar_q + eps_color) */
     float k_normal;      /* weight of max(0, 1 - n_p.n_q), and of |hit_p - hit_q| */
     float k_plane;       /* weight of |n_p.(P_q - P_p)| / (step pixel_spread max(z_p, 1e-4)) */
@@ -654,6 +685,10 @@ int ptg_denoise_host(const float *color, const float *var, const float *feat, in
  * ptg_features_device, ptg_denoise_device; then ADDS into image_rgb in
  * ptg_render's row order.  denoise NULL: the defaults with the camera's
  * pixel_spread (also taken from the camera when the given one is 0).
+ * denoise->follow_bounces, here and in every driver below (the ptg_multi
+ * ones included): 0 takes ptg_features_device, 1..16
+ * ptg_features_follow_device with that max_bounces, anything else is
+ * PTG_ERR_INVALID_ARGUMENT; ptg_denoise_device and ptg_denoise_host ignore it.
  * PTG_FLAG_EXACT_MATH and PTG_FLAG_LIGHT_SAMPLING are honoured;
  * PTG_FLAG_REFERENCE_F64 is PTG_ERR_UNSUPPORTED.  With iterations = 0 the
  * image equals ptg_render's at the same samples bit for bit. */
@@ -754,6 +789,9 @@ int ptg_render_adaptive_denoised_multi(const ptg_sphere *spheres, size_t n_spher
  * y = height - 1 - r).  Synchronous; params->shard_count must be 1. */
 int ptg_features(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
                  int device, float *features);
+/* The same for ptg_features_follow_device. */
+int ptg_features_follow(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
+                        const ptg_params *params, int device, int32_t max_bounces, float *features);
 
 /* Reassemble shard_count gathered slabs (rank-major, as all-gather lays them
  * out) into the width*height*3 image. */
