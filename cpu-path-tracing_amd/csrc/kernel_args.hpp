@@ -143,6 +143,9 @@ struct KArgs {
     // (plan_frame), which then runs the plain kernels
     const LightRec *lights;
     int n_lights;
+    // PTG_FLAG_STRATIFIED (in the struct's tail padding: no offset moves, the
+    // size stays): the launch runs the *_strat kernels
+    int stratified;
 };
 
 }  // namespace

@@ -123,6 +123,7 @@ inline void plan_frame(const ptg_params *p, int s_begin, int s_end, KArgs &A)
         A.box_mode = 0;  // the fast mode's box-mode wall test assumes rays outside the walls
     if (!(p->flags & PTG_FLAG_LIGHT_SAMPLING))
         A.n_lights = 0;  // (the scene's list stays in the context's base)
+    A.stratified = (p->flags & PTG_FLAG_STRATIFIED) != 0;
     A.n_groups = A.slab_rows * A.waves_per_row;
 }
 

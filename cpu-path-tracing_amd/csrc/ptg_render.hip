@@ -35,6 +35,7 @@
 #include "ptg_error.hpp"
 #include "ref64.hpp"
 #include "scene_prep.hpp"  // scene records, scan order, box mode, the uploads
+#include "sobol_pairs.hpp"  // PTG_FLAG_STRATIFIED: the scrambled Sobol' pairs
 
 using namespace ptg;
 
@@ -163,19 +164,37 @@ __host__ __device__ inline CamC cam_of(const KArgs &A)
                 make_float4(A.X_x, A.X_y, A.X_z, A.invW), make_float4(A.Y_x, A.Y_y, A.Y_z, A.invH)};
 }
 
+// kStrat (PTG_FLAG_STRATIFIED): the jitter is pair 0 and the lens disk's first
+// try pair 1 of the sample (cq = {pair 0, pair 1}); neither advances the
+// xorshift state, which the retries and everything after draw from.
+template <bool kStrat = false>
 __device__ __forceinline__ void camera_ray(const CamC &C, const Lane &L, uint32_t sample, uint32_t &st, f3 &o,
-                                           f3 &d)
+                                           f3 &d, [[maybe_unused]] const uint4 cq = uint4{})
 {
     st = sample_state(L.key, sample);
     // main.cpp:186-190: jitter inside the sub-pixel cell
-    float u1 = draw(st);
-    float u2 = draw(st);
+    float u1, u2;
+    if constexpr (kStrat) {
+        u1 = (float)cq.x * 0x1p-24f;
+        u2 = (float)cq.y * 0x1p-24f;
+    } else {
+        u1 = draw(st);
+        u2 = draw(st);
+    }
     float xin = __builtin_fmaf(C.b.w, u1, (float)L.x + (float)L.sx * C.b.w);
     float yin = __builtin_fmaf(C.b.w, u2, (float)L.y + (float)L.sy * C.b.w);
     float fs = xin * C.X.w;  // main.cpp:190 x/W as x * (1/W)
     float ft = yin * C.Y.w;
     // camera.cpp:19-30: rejection sample of the unit disk (2 draws per try)
     float px, py;
+    if constexpr (kStrat) {
+        px = __builtin_fmaf(2.0f, (float)cq.z * 0x1p-24f, -1.0f);
+        py = __builtin_fmaf(2.0f, (float)cq.w * 0x1p-24f, -1.0f);
+        while (__builtin_fmaf(py, py, px * px) >= 1.0f) {
+            px = __builtin_fmaf(2.0f, draw(st), -1.0f);
+            py = __builtin_fmaf(2.0f, draw(st), -1.0f);
+        }
+    } else
     do {
         px = __builtin_fmaf(2.0f, draw(st), -1.0f);
         py = __builtin_fmaf(2.0f, draw(st), -1.0f);
@@ -1078,9 +1097,11 @@ struct LsIo {
     bool shadow, skip;           // in
     bool to_shadow, skip_next;   // out
 };
-template <bool kExact, bool kLS = false>
+// kStrat (PTG_FLAG_STRATIFIED): fh holds the path's pairs 2 and 3, {phi, r,
+// u1, u2} of its first hit -- read only at depth 0, on a diffuse lane
+template <bool kExact, bool kLS = false, bool kStrat = false>
 __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2 *trig, f3 &o, f3 &d, f3 &T, f3 &E,
-                                      int &depth, uint32_t &st, LsLane &ls, LsIo &io);
+                                      int &depth, uint32_t &st, LsLane &ls, LsIo &io, const uint4 fh = uint4{});
 template <bool kExact>
 __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2 *trig, f3 &o, f3 &d, f3 &T, f3 &E,
                                       int &depth, uint32_t &st)
@@ -1090,9 +1111,10 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
     return shade<kExact, false>(hit, t, trig, o, d, T, E, depth, st, ls, io);
 }
 
-template <bool kBvh, bool kExact, bool kCount = false, bool kLS = false>
+template <bool kBvh, bool kExact, bool kCount = false, bool kLS = false, bool kStrat = false>
 __device__ __forceinline__ bool segment(const KArgs &A, const LinRec *recs, const float2 *trig, f3 &o, f3 &d, f3 &T,
-                                        f3 &E, int &depth, uint32_t &st, ScanCount &cnt, LsLane &ls, LsIo &io)
+                                        f3 &E, int &depth, uint32_t &st, ScanCount &cnt, LsLane &ls, LsIo &io,
+                                        [[maybe_unused]] const uint4 fh = uint4{})
 {
     float t;
     const ShadeRec *hit;
@@ -1107,6 +1129,9 @@ __device__ __forceinline__ bool segment(const KArgs &A, const LinRec *recs, cons
         if constexpr (kLS)
             io.hid = (int)(w - recs);
     }
+    if constexpr (kStrat)
+        return shade<kExact, kLS, true>(hit, t, trig, o, d, T, E, depth, st, ls, io, fh);
+    else
     return shade<kExact, kLS>(hit, t, trig, o, d, T, E, depth, st, ls, io);
 }
 template <bool kBvh, bool kExact, bool kCount = false>
@@ -1118,9 +1143,10 @@ __device__ __forceinline__ bool segment(const KArgs &A, const LinRec *recs, cons
     return segment<kBvh, kExact, kCount, false>(A, recs, trig, o, d, T, E, depth, st, cnt, ls, io);
 }
 
-template <bool kExact, bool kLS>
+template <bool kExact, bool kLS, bool kStrat>
 __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2 *trig, f3 &o, f3 &d, f3 &T, f3 &E,
-                                      int &depth, uint32_t &st, [[maybe_unused]] LsLane &ls, [[maybe_unused]] LsIo &io)
+                                      int &depth, uint32_t &st, [[maybe_unused]] LsLane &ls, [[maybe_unused]] LsIo &io,
+                                      [[maybe_unused]] const uint4 fh)
 {
     if constexpr (kLS) {
         // a shadow segment's "shade": the pending value when the light is
@@ -1137,6 +1163,9 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
     // (its depth is reset by the refill), so the value is only read below --
     // no per-branch copy of the loop-carried register
     depth += 1;
+    // kStrat: the camera ray's own hit takes its BRDF and light-sample draws
+    // from the path's pairs (io.fh) and leaves the xorshift state where it is
+    [[maybe_unused]] const bool first = kStrat && depth == 1;
     if (!hit) {  // main.cpp:115-120: sky
         f3 ud = norm3m<kExact>(d);
         float tt = 0.5f * (ud.y + 1.0f);
@@ -1221,11 +1250,25 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         uint32_t st_l = st;
         if (io.n_lights > 1)  // floor(u L) of u = m 2^-24, exactly
             ls_k = min((uint32_t)(io.n_lights - 1), (draw_bits(st_l) * (uint32_t)io.n_lights) >> 24);
+        [[maybe_unused]] const uint32_t st_k = st_l;  // (after the light choice, which stays xorshift)
         ls_m1 = draw_bits(st_l);
         ls_m2 = draw_bits(st_l);
+        if constexpr (kStrat) {
+            ls_m1 = first ? fh.z : ls_m1;
+            ls_m2 = first ? fh.w : ls_m2;
+            st_l = first ? st_k : st_l;
+        }
         st = ls_run ? st_l : st;
     }
-    const uint32_t m1 = draw_bits(st);
+    [[maybe_unused]] const bool sd = first & isD;  // (no roulette at depth 0: isD is the material)
+    uint32_t m1;
+    if constexpr (kStrat) {
+        uint32_t st_a = st;
+        const uint32_t mx = draw_bits(st_a);
+        m1 = sd ? fh.x : mx;
+        st = sd ? st : st_a;
+    } else
+    m1 = draw_bits(st);
     bool fres_refl = false;  // dielectric lane reflected by its Fresnel draw (isG & fres & reflect)
     // its value u = m1 2^-24, converted once for the diffuse phi (fast
     // mode: v_sin / v_cos take revolutions) and the Fresnel compare
@@ -1256,7 +1299,9 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
         // the one select after the Fresnel block; killed, mirror, totally
         // reflected and refracting lanes keep st.
         uint32_t st2 = st;
-        const uint32_t m2 = draw_bits(st2);
+        uint32_t m2 = draw_bits(st2);
+        if constexpr (kStrat)
+            m2 = sd ? fh.y : m2;
         // read only where isD (the ?: operands and the isD branch below):
         // no initial values to set for the other lanes
         float cp, sp, ra;
@@ -1307,6 +1352,9 @@ __device__ __forceinline__ bool shade(const ShadeRec *hit, float t, const float2
             spec = reflect;
         }
         // one select for the shared second step (lane masks combined by the scalar unit)
+        if constexpr (kStrat)
+            st = ((isD & !sd) || fres_refl) ? st2 : st;
+        else
         st = (isD || fres_refl) ? st2 : st;
         // op3: diffuse -> cos theta = sqrt(1 - r); dielectric -> |r_out_parallel| (main.cpp:94)
         if constexpr (!kExact) {
@@ -1501,7 +1549,16 @@ struct GatherArgs {
 // above).  Two more wave masks carry that state: smask, the lane's next
 // segment is a shadow segment; nmask, its next hit skips the listed emitters.
 // Shadow and bounce segments of different lanes share the scan iterations.
-template <bool kCount, bool kBvh, bool kExact, bool kMoments, bool kGather = false, bool kLS = false>
+//
+// kStrat (the *_strat kernels, PTG_FLAG_STRATIFIED): a path's four pairs
+// (sobol_pairs.hpp) are formed with its camera ray, in the refill batch where
+// the lanes work together, from the slot's twelve seeds in LDS (formed once
+// with its key).  Pairs 0 and 1 go into the camera ray; pairs 2 and 3 ride
+// with the prefetched ray (a third 16-byte row of the lane's record) and move
+// into the lane's first-hit row lds_fh when the path starts, which shade()
+// is handed in every iteration and reads at depth 0 only.
+template <bool kCount, bool kBvh, bool kExact, bool kMoments, bool kGather = false, bool kLS = false,
+          bool kStrat = false>
 __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *const acc2,
                                             const GatherArgs G = GatherArgs{})
 {
@@ -1510,6 +1567,11 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     __shared__ unsigned long long lds_acc2[kMoments ? kWaves : 1][kMoments ? 64 * 3 : 1];  // second moments
     __shared__ unsigned long long lds_key[kWaves][64];
     __shared__ uint32_t lds_pix[kWaves][64];  // slot -> x | sx << 20 | sy << 26
+    // kStrat: per slot the seeds {sa, sb, sc} of pairs 0..3; per lane its path's first-hit values;
+    // gather kernel: per slot the samples its pixel holds (the pairs take the absolute sample index)
+    __shared__ uint4 lds_sob[kStrat ? kWaves : 1][kStrat ? 64 : 1][3];
+    __shared__ uint4 lds_fh[kStrat ? kWaves : 1][kStrat ? 64 : 1];
+    __shared__ uint32_t lds_held[kStrat && kGather ? kWaves : 1][kStrat && kGather ? 64 : 1];
     // sphere records staged once per workgroup in LDS (uniform-address
     // ds_read_b128 broadcasts in the scan, by-id gathers at hits); larger
     // scenes read geometry with wave-uniform scalar loads from L2/HBM instead
@@ -1635,6 +1697,15 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         int sx = sub - sy * A.nsub;
         const uint64_t pix_sub = ((uint64_t)y * (uint64_t)A.W + (uint64_t)px) * (uint64_t)A.lanes_per_pixel + (uint64_t)sub;
         uint64_t key = key_hash(A.seed, pix_sub);
+        if constexpr (kStrat) {  // (from the sub-pixel's own key: the gather kernel's shift is not part of it)
+            const sobol::Seeds q0 = sobol::seeds_of(key, 0), q1 = sobol::seeds_of(key, 1), q2 = sobol::seeds_of(key, 2),
+                               q3 = sobol::seeds_of(key, 3);
+            lds_sob[wv][lane][0] = make_uint4(q0.sa, q0.sb, q0.sc, q1.sa);
+            lds_sob[wv][lane][1] = make_uint4(q1.sb, q1.sc, q2.sa, q2.sb);
+            lds_sob[wv][lane][2] = make_uint4(q2.sc, q3.sa, q3.sb, q3.sc);
+            if constexpr (kGather)
+                lds_held[wv][lane] = (uint32_t)G.counts[(size_t)slab_row * A.W + px];
+        }
         if constexpr (kGather)
             key += (uint64_t)(uint32_t)G.counts[(size_t)slab_row * A.W + px] * 0x9E3779B97F4A7C15ull;
         lds_key[wv][lane] = key;
@@ -1653,7 +1724,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     // whose path ends starts the prefetched one at once (two LDS reads), and
     // the camera code runs only in refills of >= PTG_REFILL_BATCH lanes (or
     // when a lane would otherwise idle).
-    __shared__ float4 lds_pre[kWaves][64][2];
+    __shared__ float4 lds_pre[kWaves][64][kStrat ? 3 : 2];
     // the lane's own record.  BVH kernel: its address formed at each use
     // (v_mbcnt of an opaque all-ones mask: not hoisted), not held in a VGPR
     // for the unit -- at 64 VGPRs it had been spilled and reloaded in the main
@@ -1683,7 +1754,18 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         q = r < 0 ? q - 1 : (r >= n ? q + 1 : q);
         r = r < 0 ? r + n : (r >= n ? r - n : r);
     };
-    auto ray_of = [&](int it, f3 &ro, f3 &rd, uint32_t &rs) {
+    // the lane's first-hit row (kStrat), addressed like its record
+    [[maybe_unused]] auto fh_row = [&]() -> uint4 * {
+        if constexpr (kBvh) {
+            unsigned ones = ~0u;
+            asm volatile("" : "+s"(ones));
+            const unsigned ln = __builtin_amdgcn_mbcnt_hi(ones, __builtin_amdgcn_mbcnt_lo(ones, 0u));
+            return &lds_fh[wv][ln];
+        } else {
+            return &lds_fh[wv][lane];
+        }
+    };
+    auto ray_of = [&](int it, f3 &ro, f3 &rd, uint32_t &rs, [[maybe_unused]] uint4 &fh) {
         int sl, sample;
         if (nv == 64) {
             sl = it & 63;
@@ -1707,11 +1789,26 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         int ci = 0;
         asm volatile("" : "+v"(ci));
         const CamC C{lds_cam[ci], lds_cam[ci + 1], lds_cam[ci + 2], lds_cam[ci + 3]};
+        if constexpr (kStrat) {
+            uint32_t sabs = (uint32_t)sample;
+            if constexpr (kGather)
+                sabs += lds_held[wv][sl];
+            const uint32_t brs = sobol::brev(sabs);
+            const uint4 a = lds_sob[wv][sl][0], b = lds_sob[wv][sl][1], c = lds_sob[wv][sl][2];
+            uint4 cq;
+            sobol::pair_brev(sobol::Seeds{a.x, a.y, a.z}, brs, cq.x, cq.y);
+            sobol::pair_brev(sobol::Seeds{a.w, b.x, b.y}, brs, cq.z, cq.w);
+            sobol::pair_brev(sobol::Seeds{b.z, b.w, c.x}, brs, fh.x, fh.y);
+            sobol::pair_brev(sobol::Seeds{c.y, c.z, c.w}, brs, fh.z, fh.w);
+            camera_ray<true>(C, L, (uint32_t)sample, rs, ro, rd, cq);
+        } else
         camera_ray(C, L, (uint32_t)sample, rs, ro, rd);
     };
     // (BVH scenes: a started ray is fresh -- in neither of the main loop's
     // scan-phase masks, which its lane has left by then)
-    auto begin = [&](int it, f3 ro, f3 rd, uint32_t rs) {
+    auto begin = [&](int it, f3 ro, f3 rd, uint32_t rs, [[maybe_unused]] const uint4 fh) {
+        if constexpr (kStrat)
+            *fh_row() = fh;
         if (nv == 64) {
             slot = it & 63;
         } else {
@@ -1725,8 +1822,10 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         E = mk3(0.0f, 0.0f, 0.0f);
         depth = 0;
     };
-    auto store_pre = [&](int it, f3 ro, f3 rd, uint32_t rs) {
+    auto store_pre = [&](int it, f3 ro, f3 rd, uint32_t rs, [[maybe_unused]] const uint4 fh) {
         float4 *rec = pre_rec();
+        if constexpr (kStrat)
+            rec[2] = make_float4(__uint_as_float(fh.x), __uint_as_float(fh.y), __uint_as_float(fh.z), __uint_as_float(fh.w));
         rec[0] = make_float4(ro.x, ro.y, rd.x, rd.y);
         // ro.z (= the camera's z, the lens offset has no z) rides in the
         // record's last word: read back with the ray, not as a kernel
@@ -1762,14 +1861,16 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
     if (lane < total) {
         f3 ro, rd;
         uint32_t rs;
-        ray_of(lane, ro, rd, rs);
-        begin(lane, ro, rd, rs);
+        uint4 fh{};
+        ray_of(lane, ro, rd, rs, fh);
+        begin(lane, ro, rd, rs, fh);
     }
     if (64 + lane < total) {
         f3 ro, rd;
         uint32_t rs;
-        ray_of(64 + lane, ro, rd, rs);
-        store_pre(64 + lane, ro, rd, rs);
+        uint4 fh{};
+        ray_of(64 + lane, ro, rd, rs, fh);
+        store_pre(64 + lane, ro, rd, rs, fh);
     }
     hmask = __ballot(64 + lane < total);
     int next = total < 128 ? total : 128;  // wave-uniform pool cursor
@@ -1807,6 +1908,11 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
         if (lane_in(start)) {
             const float4 *rec = pre_rec();
             const float4 p0 = rec[0], p1 = rec[1];
+            [[maybe_unused]] uint4 fh{};
+            if constexpr (kStrat) {  // the started path's first-hit values: from its record to the lane's row
+                const float4 p2 = rec[2];
+                fh = make_uint4(__float_as_uint(p2.x), __float_as_uint(p2.y), __float_as_uint(p2.z), __float_as_uint(p2.w));
+            }
             park();
             if constexpr (kStartLds) {
                 // T, depth and E read from the workgroup's constant record
@@ -1818,6 +1924,8 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
                 asm volatile("" : "+v"(so));
                 const float4 *sc = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(lds_start) + so);
                 const float4 c0 = sc[0], c1 = sc[1];
+                if constexpr (kStrat)
+                    *fh_row() = fh;
                 if (nv == 64) {
                     slot = __float_as_int(p1.z) & 63;
                 } else {
@@ -1831,7 +1939,7 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
                 depth = __float_as_int(c0.w);
                 E = mk3(c1.x, c1.y, c1.z);
             } else {
-                begin(__float_as_int(p1.z), mk3(p0.x, p0.y, p1.w), mk3(p0.z, p0.w, p1.x), __float_as_uint(p1.y));
+                begin(__float_as_int(p1.z), mk3(p0.x, p0.y, p1.w), mk3(p0.z, p0.w, p1.x), __float_as_uint(p1.y), fh);
             }
         }
         pmask |= start;
@@ -1868,17 +1976,18 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
                 if (lane_in(got)) {
                     f3 ro, rd;
                     uint32_t rs;
+                    uint4 fh{};
 #if PTG_BLOCK_STATS == 3
                     PTG_SUB_T(rr_t0);
 #endif
-                    ray_of(ni, ro, rd, rs);
+                    ray_of(ni, ro, rd, rs, fh);
 #if PTG_BLOCK_STATS == 3
                     rf_ray = clock64() - rr_t0;
 #endif
                     if (lane_in(idle))  // idle lane: start it now (its record may hold a parked path)
-                        begin(ni, ro, rd, rs);
+                        begin(ni, ro, rd, rs, fh);
                     else
-                        store_pre(ni, ro, rd, rs);
+                        store_pre(ni, ro, rd, rs, fh);
                 }
                 hmask |= got & ~idle;
                 amask |= got & idle;
@@ -1932,11 +2041,16 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
 #else
             bool done = false;
             [[maybe_unused]] LsIo io = ls_io();
+            [[maybe_unused]] uint4 fh{};
+            if constexpr (kStrat)  // (at wave level, unconditionally: selected in shade)
+                fh = *fh_row();
             if (lane_in(amask)) {
                 PTG_STAT(1);
                 if constexpr (kCount)
                     segs += 1;
-                if constexpr (kLS)
+                if constexpr (kStrat)
+                    done = segment<kBvh, kExact, kCount, kLS, true>(A, recs, trig, o, d, T, E, depth, st, scnt, ls, io, fh);
+                else if constexpr (kLS)
                     done = segment<kBvh, kExact, kCount, true>(A, recs, trig, o, d, T, E, depth, st, scnt, ls, io);
                 else
                 done = segment<kBvh, kExact, kCount>(A, recs, trig, o, d, T, E, depth, st, scnt);
@@ -2071,10 +2185,16 @@ __device__ __forceinline__ void render_unit(const KArgs A, unsigned long long *c
             const unsigned long long shade_m = rd;
             rd = 0ull;
             [[maybe_unused]] LsIo io = ls_io();
+            [[maybe_unused]] uint4 fh{};
+            if constexpr (kStrat)
+                fh = *fh_row();
             if (lane_in(shade_m)) {
                 const int sid = tr.best;
                 const ShadeRec *hrec = sid >= 0 ? A.shade + sid : nullptr;
-                if constexpr (kLS) {
+                if constexpr (kStrat) {
+                    io.hid = sid;
+                    done = shade<kExact, kLS, true>(hrec, tr.tb, trig, o, d, T, E, depth, st, ls, io, fh);
+                } else if constexpr (kLS) {
                     io.hid = sid;
                     done = shade<kExact, true>(hrec, tr.tb, trig, o, d, T, E, depth, st, ls, io);
                 } else
@@ -2245,6 +2365,31 @@ __global__ __launch_bounds__(kBlockOf<kBvh>, kMomentsWavesPerEu) void gather_ls(
                                                                                GatherArgs G)
 {
     render_unit<kCount, kBvh, kExact, true, true, true>(A, acc2, G);
+}
+
+// PTG_FLAG_STRATIFIED: the kernels above with render_unit's kStrat, with and
+// without light sampling.  The seeds, the longer records and the first-hit
+// rows take 5 KB of LDS per wave: 38-46 KB per workgroup of the linear
+// kernels, which leaves a CU 3 or 4 of them where the plain kernel runs 8, so
+// they are compiled for the 3 waves per SIMD the LDS allows (DESIGN.md
+// "Stratified sampling").  Kernels of their own: the plain and ls kernels
+// keep their names and code.
+constexpr int kStratWavesPerEu = PTG_MIN_WAVES_PER_EU < 3 ? PTG_MIN_WAVES_PER_EU : 3;
+template <bool kCount, bool kBvh, bool kExact, bool kLS>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kStratWavesPerEu) void render_strat(KArgs A)
+{
+    render_unit<kCount, kBvh, kExact, false, false, kLS, true>(A, nullptr);
+}
+template <bool kCount, bool kBvh, bool kExact, bool kLS>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kStratWavesPerEu) void moments_strat(KArgs A, unsigned long long *acc2)
+{
+    render_unit<kCount, kBvh, kExact, true, false, kLS, true>(A, acc2);
+}
+template <bool kCount, bool kBvh, bool kExact, bool kLS>
+__global__ __launch_bounds__(kBlockOf<kBvh>, kStratWavesPerEu) void gather_strat(KArgs A, unsigned long long *acc2,
+                                                                                  GatherArgs G)
+{
+    render_unit<kCount, kBvh, kExact, true, true, kLS, true>(A, acc2, G);
 }
 
 // The pixel value from the exact sums g of its sub-pixels after samps samples
@@ -2745,9 +2890,8 @@ __global__ __launch_bounds__(256) void bump_counts_kernel(int W, const int4 *__r
 }
 
 // Parity probe: one path per record {x, y, sx, sy, sample}.
-template <bool kBvh, bool kExact, bool kLS = false>
-__global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32_t *coords, int n, float *out,
-                                                         int32_t *segs_out)
+template <bool kBvh, bool kExact, bool kLS, bool kStrat>
+__device__ __forceinline__ void trace_path(const KArgs &A, const int32_t *coords, int n, float *out, int32_t *segs_out)
 {
     int i = blockIdx.x * kTraceBlock + threadIdx.x;
     if (i >= n)
@@ -2763,22 +2907,34 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32
     L.key = key_hash(A.seed, pixel_sub);
     f3 o, d;
     uint32_t st;
+    [[maybe_unused]] LsLane ls{};
+    [[maybe_unused]] LsIo io{};
+    [[maybe_unused]] uint4 fh{};
+    if constexpr (kStrat) {
+        const uint32_t brs = sobol::brev(sample);
+        uint4 cq;
+        sobol::pair_brev(sobol::seeds_of(L.key, 0), brs, cq.x, cq.y);
+        sobol::pair_brev(sobol::seeds_of(L.key, 1), brs, cq.z, cq.w);
+        sobol::pair_brev(sobol::seeds_of(L.key, 2), brs, fh.x, fh.y);
+        sobol::pair_brev(sobol::seeds_of(L.key, 3), brs, fh.z, fh.w);
+        camera_ray<true>(cam_of(A), L, sample, st, o, d, cq);
+    } else
     camera_ray(cam_of(A), L, sample, st, o, d);
     f3 T = mk3(1.0f, 1.0f, 1.0f), E = mk3(0.0f, 0.0f, 0.0f);
     int depth = 0, segs = 0;
     bool done = false;
-    [[maybe_unused]] LsLane ls{};
-    [[maybe_unused]] LsIo io{};
     while (!done) {
         segs += 1;
         ScanCount scnt;
-        if constexpr (kLS) {  // (shadow segments are scans too)
-            io.lights = A.lights;
-            io.n_lights = A.n_lights;
-            io.shadow = io.to_shadow;
-            io.skip = io.skip_next;
-            io.to_shadow = io.skip_next = false;
-            done = segment<kBvh, kExact, false, true>(A, A.lin, A.trig, o, d, T, E, depth, st, scnt, ls, io);
+        if constexpr (kLS || kStrat) {  // (shadow segments are scans too)
+            if constexpr (kLS) {
+                io.lights = A.lights;
+                io.n_lights = A.n_lights;
+                io.shadow = io.to_shadow;
+                io.skip = io.skip_next;
+                io.to_shadow = io.skip_next = false;
+            }
+            done = segment<kBvh, kExact, false, kLS, kStrat>(A, A.lin, A.trig, o, d, T, E, depth, st, scnt, ls, io, fh);
         } else
         done = segment<kBvh, kExact>(A, A.lin, A.trig, o, d, T, E, depth, st, scnt);
     }
@@ -2786,6 +2942,19 @@ __global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32
     out[3 * i + 1] = E.y;
     out[3 * i + 2] = E.z;
     segs_out[i] = segs;
+}
+template <bool kBvh, bool kExact, bool kLS = false>
+__global__ __launch_bounds__(kTraceBlock) void trace_kernel(KArgs A, const int32_t *coords, int n, float *out,
+                                                         int32_t *segs_out)
+{
+    trace_path<kBvh, kExact, kLS, false>(A, coords, n, out, segs_out);
+}
+// PTG_FLAG_STRATIFIED
+template <bool kBvh, bool kExact, bool kLS>
+__global__ __launch_bounds__(kTraceBlock) void trace_strat(KArgs A, const int32_t *coords, int n, float *out,
+                                                        int32_t *segs_out)
+{
+    trace_path<kBvh, kExact, kLS, true>(A, coords, n, out, segs_out);
 }
 
 // ptg_features_device: the first hit of the pixel's nsub^2 deterministic
@@ -2869,6 +3038,26 @@ __global__ __launch_bounds__(256) void math_probe_kernel(int op, const float *in
         Math<kExact>::sincos2pi(__float_as_uint(in[i]) & 0xFFFFFFu, trig, c, s);
         out[2 * i] = c;
         out[2 * i + 1] = s;
+    }
+}
+
+// ptg_sampler_pairs_device: PTG_FLAG_STRATIFIED's pairs 0..3 of one path per
+// record {x, y, sx, sy, sample}, as the render kernels form them
+__global__ __launch_bounds__(256) void sampler_pairs_kernel(KArgs A, const int32_t *coords, int n, uint32_t *out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint64_t pixel_sub = ((uint64_t)coords[5 * i + 1] * (uint64_t)A.W + (uint64_t)coords[5 * i + 0]) *
+                                   (uint64_t)A.lanes_per_pixel +
+                               (uint64_t)(coords[5 * i + 3] * A.nsub + coords[5 * i + 2]);
+    const uint64_t key = key_hash(A.seed, pixel_sub);
+    const uint32_t brs = sobol::brev((uint32_t)coords[5 * i + 4]);
+    for (int j = 0; j < sobol::kPairs; ++j) {
+        uint32_t m0, m1;
+        sobol::pair_brev(sobol::seeds_of(key, j), brs, m0, m1);
+        out[8 * i + 2 * j] = m0;
+        out[8 * i + 2 * j + 1] = m1;
     }
 }
 
@@ -3317,10 +3506,48 @@ int begin_launch(ptg_context *ctx, const ptg_params *p, KArgs &A, int &grid, hip
     return rc || !with_acc ? rc : ensure_acc(ctx, acc_elems_for(A), s);
 }
 
+// a run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+void with_bool(bool b, F &&f)
+{
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
+// PTG_FLAG_STRATIFIED: the *_strat kernel of the launch (G: the gather kernel's)
+int launch_strat(const KArgs &A, int grid, bool count, hipStream_t s, unsigned long long *acc2, const GatherArgs *G)
+{
+    const bool is_bvh = A.n > kLinearMax;
+    const size_t lds = is_bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
+    with_bool(A.n_lights > 0, [&](auto ls) {
+        with_bool(count, [&](auto cn) {
+            with_bool(is_bvh, [&](auto bv) {
+                with_bool(A.exact_math != 0, [&](auto ex) {
+                    constexpr bool kL = decltype(ls)::value, kC = decltype(cn)::value, kB = decltype(bv)::value,
+                                   kE = decltype(ex)::value;
+                    constexpr int kBl = kB ? PTG_BVH_BLOCK : kBlock;
+                    if (G)
+                        gather_strat<kC, kB, kE, kL><<<grid, kBl, lds, s>>>(A, acc2, *G);
+                    else if (acc2)
+                        moments_strat<kC, kB, kE, kL><<<grid, kBl, lds, s>>>(A, acc2);
+                    else
+                        render_strat<kC, kB, kE, kL><<<grid, kBl, lds, s>>>(A);
+                });
+            });
+        });
+    });
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
 int launch_render(const KArgs &A, int grid, bool count, hipStream_t s, unsigned long long *acc2 = nullptr)
 {
     if (grid <= 0)
         return PTG_OK;
+    if (A.stratified)
+        return launch_strat(A, grid, count, s, acc2, nullptr);
     const bool bvh = A.n > kLinearMax;
     const size_t lds = bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
     // the exact mode's sin/cos table has its own LDS (render_kernel)
@@ -3389,6 +3616,7 @@ int launch_ref64(const ptg_context *ctx, const KArgs &A, double *out64, float *o
     R.out32 = out32;
     R.segments = d_segments;
     R.n_lights = A.n_lights;  // (0 without PTG_FLAG_LIGHT_SAMPLING: plan_frame)
+    R.stratified = A.stratified;
     for (int k = 0; k < A.n_lights; ++k)
         R.lights[k] = ctx->light_ids[k];
     const long long waves = (long long)A.slab_rows * A.waves_per_row;
@@ -3405,6 +3633,8 @@ int launch_gather(const KArgs &A, int grid, bool count, hipStream_t s, unsigned 
 {
     if (grid <= 0)
         return PTG_OK;
+    if (A.stratified)
+        return launch_strat(A, grid, count, s, acc2, &G);
     const bool bvh = A.n > kLinearMax;
     const size_t lds = bvh ? 0 : (size_t)(A.n + 2 + 2) * sizeof(LinRec);
     switch ((A.n_lights > 0 ? 8 : 0) | (count ? 4 : 0) | (bvh ? 2 : 0) | (A.exact_math ? 1 : 0)) {
@@ -3928,7 +4158,16 @@ int ptg_trace_samples_device(ptg_context *ctx, const ptg_params *params, const i
         return rc;
     int blocks = (int)((n + kTraceBlock - 1) / kTraceBlock);
     const bool bvh = A.n > kLinearMax;
-    if (A.n_lights > 0) {  // light sampling with lights to sample
+    if (A.stratified) {
+        with_bool(A.n_lights > 0, [&](auto ls) {
+            with_bool(bvh, [&](auto bv) {
+                with_bool(A.exact_math != 0, [&](auto ex) {
+                    trace_strat<decltype(bv)::value, decltype(ex)::value, decltype(ls)::value>
+                        <<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
+                });
+            });
+        });
+    } else if (A.n_lights > 0) {  // light sampling with lights to sample
         if (A.exact_math)
             bvh ? trace_kernel<true, true, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs)
                 : trace_kernel<false, true, true><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
@@ -3941,6 +4180,28 @@ int ptg_trace_samples_device(ptg_context *ctx, const ptg_params *params, const i
     else
         bvh ? trace_kernel<true, false><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs)
             : trace_kernel<false, false><<<blocks, kTraceBlock, 0, s>>>(A, d_coords, (int)n, d_out, d_segs);
+    PTG_HIP(hipGetLastError());
+    return PTG_OK;
+}
+
+int ptg_sampler_pairs_device(ptg_context *ctx, const ptg_params *params, const int32_t *d_coords, size_t n,
+                             uint32_t *d_out, void *stream)
+{
+    if (!ctx || (n && (!d_coords || !d_out)))
+        return fail(PTG_ERR_INVALID_ARGUMENT, "NULL argument");
+    int rc = check_params(params);
+    if (rc)
+        return rc;
+    if (n > (size_t)INT32_MAX / 8)
+        return fail(PTG_ERR_UNSUPPORTED, "too many records");
+    if (n == 0)
+        return PTG_OK;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    KArgs A;
+    int grid = 0;
+    if ((rc = begin_launch(ctx, params, A, grid, s, /*with_acc=*/false)))
+        return rc;
+    sampler_pairs_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(A, d_coords, (int)n, d_out);
     PTG_HIP(hipGetLastError());
     return PTG_OK;
 }

@@ -36,6 +36,7 @@
 #include "../../include/ptgpu.h"
 #include "pt_device.hpp"
 #include "sincos_cr.hpp"
+#include "sobol_pairs.hpp"
 
 namespace ptg {
 namespace ref64 {
@@ -164,8 +165,11 @@ __device__ inline void sincos_plain(double a, double &sn, double &cs)
 // step at every diffuse hit that continues the path, with the fp32 kernels'
 // draws in their order -- the estimator's definition in double.  lights =
 // scene indices of the listed emitters.
+// fh != nullptr (PTG_FLAG_STRATIFIED): the path's pairs 2 and 3, {phi, r, u1,
+// u2} as 24-bit integers -- a diffuse hit of the camera ray takes them in
+// place of those four draws and leaves the xorshift state where it is.
 __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &st, int &segs, const int *lights = nullptr,
-                              int n_lights = 0)
+                              int n_lights = 0, const uint32_t *fh = nullptr)
 {
     d3 E = mk(0, 0, 0), T = mk(1, 1, 1);
     bool skip = false;  // this hit follows a light-sampling step: a listed emitter's front face adds no emission
@@ -210,7 +214,14 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
                     k = (int)floor(draw(st) * n_lights);
                     k = k < n_lights - 1 ? k : n_lights - 1;
                 }
-                const double u1 = draw(st), u2 = draw(st);
+                double u1, u2;
+                if (fh && depth == 0) {
+                    u1 = (double)fh[2] * 0x1p-24;
+                    u2 = (double)fh[3] * 0x1p-24;
+                } else {
+                    u1 = draw(st);
+                    u2 = draw(st);
+                }
                 const ptg_sphere &lt = s[lights[k]];
                 const d3 w = sub(ld(lt.position), h.p);
                 const double d2 = dot(w, w), R2 = lt.radius * lt.radius;
@@ -234,8 +245,15 @@ __device__ inline d3 radiance(const ptg_sphere *s, int n, d3 o, d3 d, uint32_t &
                 }
                 skip = true;
             }
-            const double phi = 2 * kPi * draw(st);
-            const double ra = draw(st);
+            double uphi, ra;
+            if (fh && depth == 0) {
+                uphi = (double)fh[0] * 0x1p-24;
+                ra = (double)fh[1] * 0x1p-24;
+            } else {
+                uphi = draw(st);
+                ra = draw(st);
+            }
+            const double phi = 2 * kPi * uphi;
             const double sth = sqrt(ra), cth = sqrt(1.0 - ra);
             const d3 w = h.n;
             const d3 u = norm(cross(fabs(w.x) > 0.1 ? mk(0, 1, 0) : mk(1, 0, 0), w));
@@ -287,6 +305,7 @@ struct Args {
     unsigned long long *segments;
     int n_lights;  // PTG_FLAG_LIGHT_SAMPLING: the light list (scene indices), 0 without the flag
     int lights[kMaxLights];
+    int stratified;  // PTG_FLAG_STRATIFIED
 };
 
 // One lane per sub-pixel: render_subpixel (main.cpp:179-197) for all samples.
@@ -311,16 +330,30 @@ __global__ __launch_bounds__(256) void render_kernel(Args A)
         const uint64_t key = key_hash(A.seed, ((uint64_t)y * (uint64_t)A.W + (uint64_t)px) * (uint64_t)A.lanes_per_pixel +
                                                   (uint64_t)subi);
         const ptg_camera &C = A.cam;
+        sobol::Seeds sd[sobol::kPairs] = {};
+        if (A.stratified)
+#pragma unroll
+            for (int j = 0; j < sobol::kPairs; ++j)
+                sd[j] = sobol::seeds_of(key, j);
         for (int k = 0; k < A.samps; ++k) {
             uint32_t st = sample_state(key, (uint32_t)k);
+            // PTG_FLAG_STRATIFIED: q[2j], q[2j + 1] = pair j of sample k
+            uint32_t q[2 * sobol::kPairs] = {};
+            if (A.stratified)
+#pragma unroll
+                for (int j = 0; j < sobol::kPairs; ++j)
+                    sobol::pair(sd[j], (uint32_t)k, q[2 * j], q[2 * j + 1]);
+            auto between_q = [&](uint32_t m, double lo, double hi) {
+                return A.stratified ? lo + (hi - lo) * ((double)m * 0x1p-24) : between(st, lo, hi);
+            };
             const double sl = 1.0 / A.nsub;
-            const double xin = (px + sx * sl + between(st, 0.0, sl));  // main.cpp:186-187
-            const double yin = (y + sy * sl + between(st, 0.0, sl));   // main.cpp:188
+            const double xin = (px + sx * sl + between_q(q[0], 0.0, sl));  // main.cpp:186-187
+            const double yin = (y + sy * sl + between_q(q[1], 0.0, sl));   // main.cpp:188
             const double s = xin / A.W, t = yin / A.H;                  // main.cpp:190
             d3 pd;
-            for (;;) {  // camera.cpp:19-30
-                const double ax = between(st, -1.0, 1.0);
-                const double ay = between(st, -1.0, 1.0);
+            for (bool first_try = true;; first_try = false) {  // camera.cpp:19-30
+                const double ax = first_try ? between_q(q[2], -1.0, 1.0) : between(st, -1.0, 1.0);
+                const double ay = first_try ? between_q(q[3], -1.0, 1.0) : between(st, -1.0, 1.0);
                 pd = mk(ax, ay, 0.0);
                 if (dot(pd, pd) >= 1.0)
                     continue;
@@ -332,7 +365,8 @@ __global__ __launch_bounds__(256) void render_kernel(Args A)
             const d3 dir = sub(sub(add(add(ld(C.lower_left_corner), mul(ld(C.cam_x_axis), s)), mul(ld(C.cam_y_axis), t)),
                                    ld(C.position)),
                                off);
-            const d3 c = radiance(A.spheres, A.n, add(ld(C.position), off), dir, st, segs, A.lights, A.n_lights);
+            const d3 c = radiance(A.spheres, A.n, add(ld(C.position), off), dir, st, segs, A.lights, A.n_lights,
+                                  A.stratified ? q + 4 : nullptr);
             acc = add(acc, mul(c, 1.0 / A.samps));  // main.cpp:192
         }
     }

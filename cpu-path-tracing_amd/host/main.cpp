@@ -6,7 +6,7 @@
 //   pt_render_gpu [--spp N] [--scene NAME|FILE] [--width W] [--height H] [--seed S]
 //                 [--devices 0,1,...] [--out FILE] [--format p3|p6]
 //                 [--save-scene FILE] [--dump-json FILE] [--no-render] [--exact-math]
-//                 [--light-sampling]
+//                 [--light-sampling] [--stratified]
 //                 [--noise-target R [--noise-floor F] [--noise-fraction Q] [--min-spp N]
 //                  [--adaptive [--dilate D] [--spp-map FILE]]]
 //                 [--denoise | --filter [--denoise-iterations N] [--denoise-follow N]]
@@ -30,6 +30,12 @@
 //            --noise-target, --adaptive and --devices.  Unbiased like the default, but the
 //            written image clamps sub-pixel means to [0, 1], which clips the default's
 //            brighter outliers more often: images of the two differ slightly in the mean.
+//   --stratified  stratified sampling (PTG_FLAG_STRATIFIED): the sub-pixel jitter, the lens point and
+//            the first hit's diffuse bounce and light sample come from a scrambled Sobol' sequence in
+//            the sample index -- less noise per sample where the first bounce matters (directly lit
+//            or depth-of-field scenes), about none deep inside a box of diffuse walls.  Combines with
+//            every other option.  The noise estimates of --noise-target and --adaptive assume
+//            independent samples and overstate the error: such frames stop later, not earlier.
 //   --noise-target R  render until converged (ptg_render_to_noise): passes of min-spp,
 //            2 min-spp, 4 min-spp, ... samples per pixel (default 64), at most --spp; stop
 //            when at most the fraction Q (default 0.01) of the pixels has a relative
@@ -245,6 +251,8 @@ int main(int argc, char *argv[])
                 flags |= PTG_FLAG_EXACT_MATH;
             else if (a == "--light-sampling")
                 flags |= PTG_FLAG_LIGHT_SAMPLING;
+            else if (a == "--stratified")
+                flags |= PTG_FLAG_STRATIFIED;
             else if (a == "--noise-target") {
                 to_noise = true;
                 target.rel_error = std::atof(val().c_str());

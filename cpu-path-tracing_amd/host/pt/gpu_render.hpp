@@ -54,7 +54,9 @@ inline int render_image(scene const &scn, camera const &cam, std::vector<vec3> &
     p.band_rows = 1;  // single-row bands: equal shards whenever shard_count divides H
     p.shard_rank = 0;
     p.shard_count = 1;
-    p.flags = flags;  // e.g. PTG_FLAG_EXACT_MATH: bit for bit the CPU oracle's image
+    // e.g. PTG_FLAG_EXACT_MATH: bit for bit the CPU oracle's image; PTG_FLAG_LIGHT_SAMPLING, PTG_FLAG_STRATIFIED
+    // (fewer samples for the same noise): every entry point of pt::gpu passes them on
+    p.flags = flags;
     return ptg_render(reinterpret_cast<ptg_sphere const *>(scn.spheres.data()), scn.spheres.size(),
                       reinterpret_cast<ptg_camera const *>(&cam), &p, device,
                       reinterpret_cast<double *>(image.data()));

@@ -21,7 +21,7 @@ EXPORTS = (
     "ptg_reset_accumulation_device", "ptg_accumulate_device", "ptg_resolve_device", "ptg_scene_layout",
     "ptg_render_multi", "ptg_multi_create", "ptg_multi_destroy", "ptg_multi_render",
     "ptg_multi_reset_accumulation", "ptg_multi_accumulate", "ptg_multi_resolve", "ptg_multi_frame_device",
-    "ptg_multi_frame_timing", "ptg_multi_image", "ptg_math_probe_device", "ptg_multi_comm_info",
+    "ptg_multi_frame_timing", "ptg_multi_image", "ptg_math_probe_device", "ptg_sampler_pairs_device", "ptg_multi_comm_info",
     "ptg_device_pci_bus_id", "ptg_launch_info",
     "ptg_noise_device", "ptg_read_moments_device", "ptg_noise_schedule", "ptg_render_to_noise",
     "ptg_set_active_mask_device", "ptg_select_active_device", "ptg_accumulate_active_device",
@@ -121,6 +121,7 @@ def lib():
             "ptg_tonemap_device": (I, [P, P, C.c_size_t, P]),
             "ptg_trace_samples_device": (I, [P, C.POINTER(Params), P, C.c_size_t, P, P, P]),
             "ptg_math_probe_device": (I, [P, C.c_int32, C.c_int32, P, P, C.c_size_t, P]),
+            "ptg_sampler_pairs_device": (I, [P, C.POINTER(Params), P, C.c_size_t, P, P]),
             "ptg_reset_accumulation_device": (I, [P, C.POINTER(Params), P]),
             "ptg_accumulate_device": (I, [P, C.POINTER(Params), C.c_int32, C.c_int32, P, P]),
             "ptg_resolve_device": (I, [P, C.POINTER(Params), C.c_int32, P, P]),

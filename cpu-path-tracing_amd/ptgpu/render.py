@@ -63,6 +63,9 @@ FLAG_MOMENTS = 16  # include/ptgpu.h PTG_FLAG_MOMENTS: progressive passes also s
 # Unbiased like the plain estimator: compare the two on raw sums (Context.read_moments), not on clamped images
 FLAG_LIGHT_SAMPLING = 32
 MAX_LIGHTS = 16  # include/ptgpu.h PTG_MAX_LIGHTS
+# include/ptgpu.h PTG_FLAG_STRATIFIED: four pairs of draws per path (jitter, lens, the first hit's diffuse bounce
+# and light sample) from a scrambled Sobol' (0,2)-sequence in the sample index (Context.sampler_pairs)
+FLAG_STRATIFIED = 64
 
 
 def _n_counters(flags: int) -> int:
@@ -452,7 +455,7 @@ class MultiContext:
 # every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel) and
 # follow_features.hpp (the followed-feature kernel): neither holds a timed kernel
 KERNEL_SOURCES = ("ptg_render.hip", "pt_device.hpp", "bvh_build.hpp", "kernel_args.hpp", "scene_prep.hpp",
-                  "launch_plan.hpp", "ptg_error.hpp")
+                  "launch_plan.hpp", "ptg_error.hpp", "sobol_pairs.hpp")
 
 
 def kernel_source_hash() -> str:
@@ -782,6 +785,22 @@ class Context:
                                              C.c_void_p(out.data_ptr()), C.c_void_p(segs.data_ptr()),
                                              C.c_void_p(s)), "ptg_trace_samples_device")
         return out, segs
+
+    def sampler_pairs(self, coords, params: Params):
+        """FLAG_STRATIFIED's pairs 0..3 of individual paths (coords: int32
+        CUDA tensor [n, 5] = x, y, sx, sy, sample) -> int32 [n, 4, 2], the
+        24-bit integers (m0, m1) of each pair (ptg_sampler_pairs_device)."""
+        import torch
+        if coords.dim() != 2 or coords.shape[1] != 5:
+            raise ValueError("coords must be [n, 5] (x, y, sx, sy, sample)")
+        coords = coords.contiguous()
+        self._check(coords, torch.int32, coords.numel())
+        n = coords.shape[0]
+        out = torch.empty((n, 4, 2), dtype=torch.int32, device=coords.device)
+        check(lib().ptg_sampler_pairs_device(self._h, C.byref(params), C.c_void_p(coords.data_ptr()), n,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(self._stream(None))),
+              "ptg_sampler_pairs_device")
+        return out
 
     PROBE_OPS = {"sqrt": 0, "rsqrt": 1, "div": 2, "sincos": 3}  # include/ptgpu.h PTG_PROBE_*
 

@@ -192,6 +192,54 @@ typedef struct ptg_params {
  * the two.  Compare estimators on the raw sums (ptg_read_moments_device). */
 #define PTG_FLAG_LIGHT_SAMPLING 32
 #define PTG_MAX_LIGHTS 16
+/* PTG_FLAG_STRATIFIED: stratified sampling.  Four pairs of draws per path
+ * come from an Owen-scrambled, index-shuffled Sobol' (0,2)-sequence in the
+ * path's sample index s instead of the xorshift stream.  Without the flag
+ * nothing changes: the same draws, the same kernels, the same images.
+ * Honoured wherever PTG_FLAG_LIGHT_SAMPLING is (every entry point that
+ * renders, trace_samples, the ptg_multi_* family, PTG_FLAG_REFERENCE_F64) and
+ * combines with it.  A frame still does not depend on sharding, work-unit
+ * sizes, progressive passes or the GPU count: a pixel that holds n samples
+ * holds samples [0, n), and a (0,2)-sequence is stratified on every
+ * power-of-two prefix of that index.
+ *
+ * The definition (csrc/sobol_pairs.hpp), integer arithmetic on uint32 but for
+ * the 64-bit seed mix:
+ *   lk(x, seed):  x += seed; x ^= x*0x6c50b47c; x ^= x*0xb82f1e52;
+ *                 x ^= x*0xc7afe638; x ^= x*0x8d22f6e6
+ *   brev:         32-bit bit reversal
+ *   P(i):         for (k, m) in (1,0x55555555),(2,0x33333333),(4,0x0F0F0F0F),
+ *                 (8,0x00FF00FF),(16,0x0000FFFF): i ^= (i >> k) & m
+ *                 (= brev of the second Sobol' dimension of i, direction
+ *                 numbers v = 1<<31; v ^= v>>1 per index bit)
+ *   seeds of pair j of a sub-pixel, key = key_hash(seed, pixel_sub) as for
+ *   the xorshift stream, mix64 its mixer:
+ *                 h = mix64(key ^ (j+1)*0xD1B54A32D192ED03)
+ *                 sa = hi32(h), sb = lo32(h), sc = hi32(mix64(h))
+ *   pair j, sample s:
+ *                 i  = brev(lk(brev(s), sa))       (the shuffled index)
+ *                 m0 = brev(lk(i, sb)) >> 8        (van der Corput, scrambled)
+ *                 m1 = brev(lk(P(i), sc)) >> 8     (Sobol' dimension 2, scrambled)
+ * m0 and m1 are 24-bit integers used exactly where a draw's 24-bit integer
+ * is: u = m 2^-24.  Every aligned block of 2^k samples of a pair puts one
+ * point in each elementary interval of area 2^-k.
+ *
+ * Which draws, by pair number:
+ *   0. the sub-pixel jitter (main.cpp:186-188)
+ *   1. the first try of the lens disk's rejection loop (camera.cpp:19-30);
+ *      retries stay xorshift
+ *   2. the diffuse sampler's (phi, r) at the camera ray's own hit, when that
+ *      hit is diffuse
+ *   3. with PTG_FLAG_LIGHT_SAMPLING, that same hit's (u1, u2) of step 2 of the
+ *      light-sampling step; the light choice of step 1 stays xorshift
+ * Every other draw is xorshift from sample_state(key, s) as without the flag,
+ * and a replaced draw does not advance the xorshift state.  A first hit on a
+ * mirror or glass gets no stratified bounce.
+ *
+ * ptg_noise_device and the adaptive selection assume independent samples, so
+ * with the flag they overstate the error: noise-target and adaptive frames
+ * stop later rather than earlier, and no image is wrong. */
+#define PTG_FLAG_STRATIFIED 64
 
 typedef struct ptg_context ptg_context;
 
@@ -845,6 +893,14 @@ int ptg_trace_samples_device(ptg_context *ctx, const ptg_params *params, const i
 #define PTG_PROBE_SINCOS 3
 int ptg_math_probe_device(ptg_context *ctx, int32_t op, int32_t exact, const float *d_in, float *d_out, size_t n,
                           void *stream);
+
+/* Probe of PTG_FLAG_STRATIFIED's sampler: for n records {x, y, sx, sy,
+ * sample} (int32 each, as ptg_trace_samples_device takes them) d_out receives
+ * 8 uint32 per record, {m0, m1} of pairs 0..3 of that path under params'
+ * seed, width and num_subpixels -- the integers the render kernels form,
+ * whatever params->flags says. */
+int ptg_sampler_pairs_device(ptg_context *ctx, const ptg_params *params, const int32_t *d_coords, size_t n,
+                             uint32_t *d_out, void *stream);
 
 #ifdef __cplusplus
 }

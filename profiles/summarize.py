@@ -146,6 +146,9 @@ def main(src, tag, kernel_sub="render_kernel"):
         if "valu_fp32_share" in out:
             rf["valu_fp32_share"] = round(out["valu_fp32_share"], 4)
         rf["profile"] = tag
+        # (a warning that the run-time fields were another kernel's goes with them)
+        if "profile_warning" in rf:
+            rf["pmc_fields_at_run_time"]["profile_warning"] = rf.pop("profile_warning")
     dst = os.path.join(os.path.dirname(os.path.abspath(__file__)), f"{tag}_summary.json")
     with open(dst, "w") as f:
         json.dump(out, f, indent=1)
