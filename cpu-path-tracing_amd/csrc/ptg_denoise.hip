@@ -1,8 +1,8 @@
 // ptg_denoise.hip -- the variance-guided a-trous filter of include/ptgpu.h
-// ("denoising"): its kernels, the C ABI around them and the render-and-denoise
-// driver.  The arithmetic is denoise_filter.hpp's, shared with the host loop;
-// this file needs no context -- the driver goes through the public entry
-// points of ptg_render.hip.
+// ("denoising"): its kernels and the C ABI around them.  The arithmetic is
+// denoise_filter.hpp's, shared with the host loop; this file needs no context
+// -- the render-and-denoise drivers are csrc/ptg_frames.cpp's and
+// csrc/ptg_multi.cpp's.
 //
 // Kernels: one thread per pixel, workgroups of 64 x 4 pixels (a wave's lanes
 // contiguous in x).  dn_filter_tiled_kernel stages the taps in LDS (steps up
@@ -332,7 +332,7 @@ int ptg_features_follow(const ptg_sphere *spheres, size_t n_spheres, const ptg_c
     return features_host(spheres, n_spheres, cam, params, device, max_bounces, features);
 }
 
-// internal (the drivers here and in csrc/ptg_multi.cpp): the filter's parameters a driver runs with -- `denoise`,
+// internal (the drivers in csrc/ptg_frames.cpp and csrc/ptg_multi.cpp): the filter's parameters a driver runs with -- `denoise`,
 // or the defaults when it is NULL, with the camera's pixel_spread when it is NULL or gives 0 -- checked
 int ptg_denoise_params_for_(const ptg_camera *cam, int32_t width, int32_t height, const ptg_denoise_params *denoise,
                             ptg_denoise_params *out)
@@ -360,278 +360,6 @@ int ptg_features_for_(ptg_context *ctx, const ptg_params *params, const ptg_deno
 {
     return k->follow_bounces ? ptg_features_follow_device(ctx, params, k->follow_bounces, d_feat, stream)
                              : ptg_features_device(ctx, params, d_feat, stream);
-}
-
-}  // extern "C"
-
-namespace {
-
-// Both drivers: the frame's passes with PTG_FLAG_MOMENTS -- one pass over [0, samples), or with a target the
-// passes of ptg_noise_schedule, each followed by one ptg_noise_device check as ptg_render_to_noise makes it --
-// then resolve, variance slab, features, filter, and the ADD into the image.
-int render_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
-                    int device, const ptg_denoise_params *denoise, const ptg_noise_target *target, double *image_rgb,
-                    ptg_noise_report *report)
-{
-    if (!image_rgb || !params || !cam)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised: NULL image, camera or params");
-    if (params->width <= 0 || params->height <= 0)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (params->shard_count != 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised: shard_count must be 1 (the filter needs the "
-                                              "whole frame)");
-    if (params->samples < 2)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised: samples must be >= 2 (the variance needs two)");
-    if (params->flags & PTG_FLAG_REFERENCE_F64)
-        return fail(PTG_ERR_UNSUPPORTED, "render_denoised: fp32 only (no progressive passes in the "
-                                         "reference-arithmetic mode)");
-    int rc;
-    int32_t ends[PTG_NOISE_MAX_PASSES] = {params->samples}, n_ends = 1;
-    if (target) {
-        if (!(target->floor > 0.0) || !(target->rel_error >= 0.0))
-            return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: floor must be > 0 and rel_error >= 0");
-        if (!(target->max_fraction >= 0.0 && target->max_fraction < 1.0))
-            return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: max_fraction must be in [0, 1)");
-        if ((rc = ptg_noise_schedule(target->min_samples, params->samples, ends, PTG_NOISE_MAX_PASSES, &n_ends)))
-            return rc;
-    }
-    ptg_denoise_params k;
-    if ((rc = ptg_denoise_params_for_(cam, params->width, params->height, denoise, &k)))
-        return rc;
-    ptg_context *ctx = nullptr;
-    if ((rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx)))
-        return rc;
-    const int W = params->width, H = params->height;
-    int32_t rows = 0;
-    size_t scratch_bytes = 0;
-    float *d_buf = nullptr;
-    std::vector<float> host((size_t)H * W * 3);
-    ptg_noise_report rep{};
-    ptg_params p = *params;
-    p.flags |= PTG_FLAG_MOMENTS;
-    // everything on the null stream, in order; each check's 32 bytes copied back synchronously
-    auto run = [&]() -> int {
-        int r;
-        if ((r = ptg_shard_rows(H, p.band_rows, 1, &rows)) || (r = ptg_denoise_scratch_bytes(W, H, &scratch_bytes)))
-            return r;
-        // one allocation: the check's statistics, the features, the colour, variance and output slabs, the
-        // scratch -- every part starts at a multiple of 64 floats (256 B: ptg_features_device stores float4,
-        // the statistics are 64-bit atomics), whatever rows * W is
-        const auto part = [](size_t floats) { return (floats + 63) / 64 * 64; };
-        const size_t stats = part(8), feat = part((size_t)rows * W * kFeat), slab = part((size_t)rows * W * 3);
-        const size_t total = stats + feat + 3 * slab + part(scratch_bytes / sizeof(float));
-        if (hipMalloc(&d_buf, total * sizeof(float)) != hipSuccess)
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the denoiser's frames failed");
-        unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_buf);
-        float *d_feat = d_buf + stats, *d_color = d_feat + feat, *d_var = d_color + slab, *d_out = d_var + slab;
-        float *d_scratch = d_out + slab;
-        if ((r = ptg_reset_accumulation_device(ctx, &p, nullptr)))
-            return r;
-        int32_t done = 0;
-        for (int i = 0; i < n_ends; ++i) {
-            if ((r = ptg_accumulate_device(ctx, &p, done, ends[i], nullptr, nullptr)))
-                return r;
-            done = ends[i];
-            if (!target)
-                break;
-            unsigned long long st[4] = {0, 0, 0, 0};
-            PTG_DN_HIP(hipMemsetAsync(d_stats, 0, sizeof(st), nullptr));
-            if ((r = ptg_noise_device(ctx, &p, done, target->rel_error, target->floor, nullptr, nullptr, d_stats,
-                                      nullptr)))
-                return r;
-            PTG_DN_HIP(hipMemcpy(st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
-            rep.samples_done = done;
-            rep.passes = i + 1;
-            rep.pixels = st[3];
-            rep.pixels_over = st[0];
-            rep.pass_samples[i] = done;
-            rep.pass_over[i] = st[0];
-            const uint32_t max_bits = (uint32_t)st[2];
-            float max_rho;
-            std::memcpy(&max_rho, &max_bits, sizeof(max_rho));
-            rep.max_rho = (double)max_rho;
-            rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
-            rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
-            if (rep.converged)
-                break;
-        }
-        if ((r = ptg_resolve_device(ctx, &p, done, d_color, nullptr)) ||
-            (r = ptg_noise_device(ctx, &p, done, 0.0, 1.0, d_var, nullptr, nullptr, nullptr)) ||
-            (r = ptg_features_for_(ctx, &p, &k, d_feat, nullptr)) ||
-            (r = ptg_denoise_device(d_color, d_var, d_feat, W, H, &k, d_out, nullptr, d_scratch, scratch_bytes,
-                                    nullptr)))
-            return r;
-        PTG_DN_HIP(hipMemcpy(host.data(), d_out, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        return PTG_OK;
-    };
-    rc = run();
-    if (d_buf)
-        (void)hipFree(d_buf);
-    ptg_context_destroy(ctx);
-    if (rc)
-        return rc;
-    for (size_t i = 0; i < host.size(); ++i)  // shard_count 1: slab row j is image row j
-        image_rgb[i] = image_rgb[i] + (double)host[i];
-    if (report)
-        *report = rep;
-    return PTG_OK;
-}
-
-// ptg_render_adaptive's frame -- its schedule, checks, stop rule, report and counts, over the same public entry
-// points -- then, on the frame it stopped at: resolve with each pixel's own count, the variance slab with each
-// pixel's own count, features, filter, and the ADD into the image.
-int render_adaptive_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
-                             const ptg_params *params, int device, const ptg_adaptive_target *target,
-                             const ptg_denoise_params *denoise, double *image_rgb, int32_t *sample_counts,
-                             ptg_adaptive_report *report)
-{
-    if (!image_rgb || !params || !cam || !target)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised: NULL image, camera, params or target");
-    if (params->width <= 0 || params->height <= 0)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "width and height must be positive");
-    if (!(target->floor > 0.0) || !(target->rel_error >= 0.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised: floor must be > 0 and rel_error >= 0");
-    if (!(target->max_fraction >= 0.0 && target->max_fraction < 1.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised: max_fraction must be in [0, 1)");
-    if (target->dilate < 0 || target->dilate > 8)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised: dilate must be in [0, 8]");
-    if (params->shard_count != 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised: shard_count must be 1 (the filter needs "
-                                              "the whole frame)");
-    if (params->flags & PTG_FLAG_REFERENCE_F64)
-        return fail(PTG_ERR_UNSUPPORTED, "render_adaptive_denoised: progressive passes are fp32 only");
-    int rc;
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    if ((rc = ptg_noise_schedule(target->min_samples, params->samples, ends, PTG_NOISE_MAX_PASSES, &n_ends)))
-        return rc;
-    ptg_denoise_params k;
-    if ((rc = ptg_denoise_params_for_(cam, params->width, params->height, denoise, &k)))
-        return rc;
-    ptg_context *ctx = nullptr;
-    if ((rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx)))
-        return rc;
-    const ptg_params &p = *params;
-    const int W = p.width, H = p.height;
-    const bool count = (p.flags & (PTG_FLAG_COUNT_TESTS | PTG_FLAG_COUNT_NONFINITE)) != 0;
-    int32_t rows = 0;
-    size_t scratch_bytes = 0;
-    float *d_buf = nullptr;
-    std::vector<float> host((size_t)H * W * 3);
-    std::vector<int32_t> host_counts(sample_counts ? (size_t)H * W : 0);
-    ptg_adaptive_report rep{};
-    // everything on the null stream, in order; each selection's 48 bytes copied back synchronously
-    auto run = [&]() -> int {
-        int r;
-        if ((r = ptg_shard_rows(H, p.band_rows, 1, &rows)) || (r = ptg_denoise_scratch_bytes(W, H, &scratch_bytes)))
-            return r;
-        // one allocation, every part at a multiple of 64 floats (256 B) as in render_denoised: the 6 statistics
-        // and 4 kernel counters, the features, the colour, variance and output slabs, the counts, the scratch
-        const auto part = [](size_t floats) { return (floats + 63) / 64 * 64; };
-        const size_t stats = part(2 * 10), feat = part((size_t)rows * W * kFeat), slab = part((size_t)rows * W * 3);
-        const size_t cnt = part((size_t)rows * W);
-        const size_t total = stats + feat + 3 * slab + cnt + part(scratch_bytes / sizeof(float));
-        if (hipMalloc(&d_buf, total * sizeof(float)) != hipSuccess)
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the denoiser's frames failed");
-        unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_buf);
-        float *d_feat = d_buf + stats, *d_color = d_feat + feat, *d_var = d_color + slab, *d_out = d_var + slab;
-        int32_t *d_cnt = reinterpret_cast<int32_t *>(d_out + slab);
-        float *d_scratch = d_out + slab + cnt;
-        PTG_DN_HIP(hipMemsetAsync(d_stats, 0, 10 * sizeof(unsigned long long), nullptr));
-        unsigned long long *d_seg = count ? d_stats + 6 : nullptr;
-        if ((r = ptg_reset_accumulation_device(ctx, &p, nullptr)) ||
-            (r = ptg_set_active_mask_device(ctx, &p, nullptr, nullptr, nullptr)))  // pass 0: every pixel
-            return r;
-        unsigned long long active = (unsigned long long)W * H;
-        long long units = 0;  // pass 0: the host-side bound
-        int32_t done = 0;
-        for (int i = 0; i < n_ends; ++i) {
-            unsigned long long st[6] = {0, 0, 0, 0, 0, 0};
-            PTG_DN_HIP(hipMemsetAsync(d_stats, 0, sizeof(st), nullptr));
-            const int32_t add = ends[i] - done;
-            if ((r = ptg_accumulate_active_device(ctx, &p, add, units, d_seg, nullptr)))
-                return r;
-            done = ends[i];
-            rep.total_samples += active * (unsigned long long)add;
-            if ((r = ptg_select_active_device(ctx, &p, target->rel_error, target->floor, target->dilate, nullptr,
-                                              d_stats, nullptr)))
-                return r;
-            PTG_DN_HIP(hipMemcpy(st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
-            rep.passes = i + 1;
-            rep.max_samples = done;
-            rep.pixels = st[3];
-            rep.pixels_over = st[0];
-            rep.pass_added[i] = add;
-            rep.pass_over[i] = st[0];
-            rep.pass_active[i] = st[4];
-            const uint32_t max_bits = (uint32_t)st[2];
-            float max_rho;
-            std::memcpy(&max_rho, &max_bits, sizeof(max_rho));
-            rep.max_rho = (double)max_rho;
-            rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
-            rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
-            if (rep.converged)
-                break;
-            active = st[4];
-            units = (long long)st[5];  // (> 0: a pixel over the target is active)
-        }
-        if ((r = ptg_resolve_active_device(ctx, &p, d_color, nullptr)) ||
-            (r = ptg_noise_active_device(ctx, &p, 1.0, d_var, nullptr, nullptr)) ||
-            (r = ptg_features_for_(ctx, &p, &k, d_feat, nullptr)) ||
-            (r = ptg_denoise_device(d_color, d_var, d_feat, W, H, &k, d_out, nullptr, d_scratch, scratch_bytes,
-                                    nullptr)))
-            return r;
-        if (sample_counts) {
-            if ((r = ptg_read_sample_counts_device(ctx, &p, d_cnt, nullptr)))
-                return r;
-            PTG_DN_HIP(hipMemcpy(host_counts.data(), d_cnt, host_counts.size() * sizeof(int32_t),
-                                 hipMemcpyDeviceToHost));
-        }
-        if (count)
-            PTG_DN_HIP(hipMemcpy(rep.counters, d_stats + 6, sizeof(rep.counters), hipMemcpyDeviceToHost));
-        PTG_DN_HIP(hipMemcpy(host.data(), d_out, host.size() * sizeof(float), hipMemcpyDeviceToHost));
-        return PTG_OK;
-    };
-    rc = run();
-    if (d_buf)
-        (void)hipFree(d_buf);
-    ptg_context_destroy(ctx);
-    if (rc)
-        return rc;
-    for (size_t i = 0; i < host.size(); ++i)  // shard_count 1: slab row j is image row j
-        image_rgb[i] = image_rgb[i] + (double)host[i];
-    if (sample_counts)
-        std::memcpy(sample_counts, host_counts.data(), host_counts.size() * sizeof(int32_t));
-    if (report)
-        *report = rep;
-    return PTG_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ptg_render_adaptive_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
-                                 const ptg_params *params, int device, const ptg_adaptive_target *target,
-                                 const ptg_denoise_params *denoise, double *image_rgb, int32_t *sample_counts,
-                                 ptg_adaptive_report *report)
-{
-    return render_adaptive_denoised(spheres, n_spheres, cam, params, device, target, denoise, image_rgb,
-                                    sample_counts, report);
-}
-
-int ptg_render_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
-                        int device, const ptg_denoise_params *denoise, double *image_rgb)
-{
-    return render_denoised(spheres, n_spheres, cam, params, device, denoise, nullptr, image_rgb, nullptr);
-}
-
-int ptg_render_to_noise_denoised(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
-                                 const ptg_params *params, int device, const ptg_noise_target *target,
-                                 const ptg_denoise_params *denoise, double *image_rgb, ptg_noise_report *report)
-{
-    if (!target)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise_denoised: NULL target");
-    return render_denoised(spheres, n_spheres, cam, params, device, denoise, target, image_rgb, report);
 }
 
 }  // extern "C"

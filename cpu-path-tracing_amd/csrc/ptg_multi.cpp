@@ -29,10 +29,8 @@
 #include <vector>
 
 #include "../../include/ptgpu.h"
+#include "frame_passes.hpp"  // the drivers' checks, pass loops and report fillers; fail() (ptg_last_error's channel)
 
-// ptg_last_error is thread-local in ptg_render.hip; errors raised here go
-// through the same channel
-extern "C" int ptg_set_error_(int code, const char *msg);
 // csrc/ptg_denoise.hip: the filter parameters a driver runs with (NULL: the
 // defaults; the camera's pixel_spread where none is given), checked
 extern "C" int ptg_denoise_params_for_(const ptg_camera *cam, int32_t width, int32_t height,
@@ -42,7 +40,7 @@ extern "C" int ptg_features_for_(ptg_context *ctx, const ptg_params *params, con
 
 namespace {
 
-int fail(int code, const std::string &msg) { return ptg_set_error_(code, msg.c_str()); }
+using namespace ptg_frames;
 
 struct Shard {
     int id = -1;  // HIP device
@@ -467,13 +465,6 @@ int gather_unshard(ptg_multi *m, const ptg_params *p, size_t slab_elems)
 // host is to hand every shard the whole frame's over bytes and to decide for
 // the frame.
 
-int check_noise_args(double rel_error, double floor, const char *who)
-{
-    if (!(floor > 0.0) || !(rel_error >= 0.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": floor must be > 0 and rel_error >= 0");
-    return PTG_OK;
-}
-
 // the per-shard byte slabs, statistics and count slab for a frame of this
 // size (grown, never shrunk), the pinned statistics of all shards
 int reserve_adaptive(ptg_multi *m, const ptg_params *p, size_t &slab_pixels)
@@ -663,7 +654,8 @@ int multi_accumulate_active(ptg_multi *m, const ptg_params *p, int32_t add_sampl
     return PTG_OK;
 }
 
-int multi_resolve_active(ptg_multi *m, const ptg_params *p)  // into m->host
+// the sums resolved into m->host: at samples_done, or (active) each pixel at its own count
+int multi_resolve(ptg_multi *m, const ptg_params *p, int32_t samples_done, bool active = false)
 {
     size_t slab_elems = 0;
     int rc = reserve(m, p, slab_elems);
@@ -671,8 +663,10 @@ int multi_resolve_active(ptg_multi *m, const ptg_params *p)  // into m->host
         return rc;
     const int n = (int)m->shards.size();
     for (int k = 0; k < n; ++k) {
+        Shard &s = m->shards[k];
         const ptg_params q = shard_params(p, k, n);
-        if ((rc = ptg_resolve_active_device(m->shards[k].ctx, &q, m->shards[k].slab, m->shards[k].stream)))
+        if ((rc = active ? ptg_resolve_active_device(s.ctx, &q, s.slab, s.stream)
+                         : ptg_resolve_device(s.ctx, &q, samples_done, s.slab, s.stream)))
             return rc;
     }
     return gather_unshard(m, p, slab_elems);
@@ -812,25 +806,26 @@ int multi_resolve_filtered(ptg_multi *m, const ptg_params *p, int32_t samples_do
     return sync_all(m);
 }
 
-double rho_of_bits(unsigned long long bits)
-{
-    const uint32_t b = (uint32_t)bits;
-    float rho;
-    std::memcpy(&rho, &b, sizeof(rho));
-    return (double)rho;
-}
+// The loops' steps (frame_passes.hpp) from a ptg_multi: each check's statistics are every shard's, combined,
+// with one synchronisation; a pass is bounded by each shard's own unit count (multi_select), not the frame's.
+struct MultiSteps {
+    ptg_multi *m;
+    const ptg_params &p;
+    bool count;  // adaptive passes add to the shards' kernel counters
 
-// the drivers' argument checks after the frame's (before any device work); the pass ends
-int check_driver(const ptg_params *p, double rel_error, double floor, double max_fraction, int32_t min_samples,
-                 const char *who, int32_t *ends, int32_t *n_ends)
-{
-    int rc = check_noise_args(rel_error, floor, who);
-    if (rc)
-        return rc;
-    if (!(max_fraction >= 0.0 && max_fraction < 1.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, std::string(who) + ": max_fraction must be in [0, 1)");
-    return ptg_noise_schedule(min_samples, p->samples, ends, PTG_NOISE_MAX_PASSES, n_ends);
-}
+    int reset() { return ptg_multi_reset_accumulation(m, &p); }
+    int accumulate(int32_t b, int32_t e) { return ptg_multi_accumulate(m, &p, b, e); }
+    int noise(int32_t done, double rel_error, double floor, unsigned long long *st)
+    {
+        return multi_noise(m, &p, done, rel_error, floor, st);
+    }
+    int all_active() { return multi_set_mask(m, &p, nullptr); }
+    int accumulate_active(int32_t add, long long) { return multi_accumulate_active(m, &p, add, count); }
+    int select(double rel_error, double floor, int32_t dilate, unsigned long long *st)
+    {
+        return multi_select(m, &p, rel_error, floor, dilate, st);
+    }
+};
 
 }  // namespace
 
@@ -877,9 +872,7 @@ int ptg_multi_render(ptg_multi *m, const ptg_params *params, double *image_rgb)
     }
     if ((rc = gather_unshard(m, params, slab_elems)))
         return rc;
-    const size_t image_elems = (size_t)params->width * params->height * 3;
-    for (size_t i = 0; i < image_elems; ++i)
-        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
+    add_image(image_rgb, m->host.data(), (size_t)params->width * params->height * 3);
     return PTG_OK;
 }
 
@@ -925,16 +918,7 @@ int ptg_multi_resolve(ptg_multi *m, const ptg_params *params, int32_t samples_do
     if (!image_rgb)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_resolve: image is NULL");
     DeviceGuard g;
-    size_t slab_elems = 0;
-    if ((rc = reserve(m, params, slab_elems)))
-        return rc;
-    const int n = (int)m->shards.size();
-    for (int k = 0; k < n; ++k) {
-        const ptg_params q = shard_params(params, k, n);
-        if ((rc = ptg_resolve_device(m->shards[k].ctx, &q, samples_done, m->shards[k].slab, m->shards[k].stream)))
-            return rc;
-    }
-    if ((rc = gather_unshard(m, params, slab_elems)))
+    if ((rc = multi_resolve(m, params, samples_done)))
         return rc;
     const size_t image_elems = (size_t)params->width * params->height * 3;
     std::copy(m->host.begin(), m->host.begin() + image_elems, image_rgb);
@@ -951,7 +935,7 @@ int ptg_multi_noise(ptg_multi *m, const ptg_params *params, int32_t samples_done
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_noise: stats is NULL");
     if (samples_done < 2 || samples_done > params->samples)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_noise: samples_done must be in [2, samples]");
-    if ((rc = check_noise_args(rel_error, floor, "multi_noise")))
+    if ((rc = check_noise_args("multi_noise", rel_error, floor)))
         return rc;
     m->timed = false;  // the image / events no longer describe a frame_device frame
     DeviceGuard g;
@@ -972,7 +956,7 @@ int ptg_multi_select_active(ptg_multi *m, const ptg_params *params, double rel_e
                             unsigned long long *stats)
 {
     int rc = check_frame(m, params);
-    if (rc || (rc = check_noise_args(rel_error, floor, "multi_select_active")))
+    if (rc || (rc = check_noise_args("multi_select_active", rel_error, floor)))
         return rc;
     if (dilate < 0 || dilate > 8)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_select_active: dilate must be in [0, 8]");
@@ -1002,7 +986,7 @@ int ptg_multi_resolve_active(ptg_multi *m, const ptg_params *params, float *imag
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_resolve_active: image is NULL");
     m->timed = false;
     DeviceGuard g;
-    if ((rc = multi_resolve_active(m, params)))
+    if ((rc = multi_resolve(m, params, 0, /*active=*/true)))
         return rc;
     const size_t image_elems = (size_t)params->width * params->height * 3;
     std::copy(m->host.begin(), m->host.begin() + image_elems, image_rgb);
@@ -1021,71 +1005,41 @@ int ptg_multi_read_sample_counts(ptg_multi *m, const ptg_params *params, int32_t
     return multi_read_counts(m, params, counts);
 }
 
-// ptg_multi_render_to_noise, and with `denoise` ptg_multi_render_to_noise_denoised: the same passes, checks and
-// report, the frame it stopped at through the filter
+// The noise-target frames, their arguments checked: the passes, checks and report of frame_passes.hpp (no
+// target: the one pass [0, samples) of ptg_multi_render_denoised), the frame they stopped at resolved -- through
+// the filter `dk` where there is one -- and ADDED into image_rgb
+static int noise_frame_on(ptg_multi *m, const ptg_params *params, const Passes &ps, const ptg_noise_target *target,
+                          const ptg_denoise_params *dk, double *image_rgb, ptg_noise_report *report)
+{
+    m->timed = false;
+    DeviceGuard g;
+    ptg_noise_report rep{};
+    ptg_params p = *params;
+    p.flags |= PTG_FLAG_MOMENTS;
+    int32_t done = 0;
+    int rc = noise_passes(MultiSteps{m, p, false}, ps, target, rep, done);
+    if (rc || (rc = dk ? multi_resolve_filtered(m, &p, done, *dk) : multi_resolve(m, &p, done)))
+        return rc;
+    add_image(image_rgb, m->host.data(), (size_t)p.width * p.height * 3);
+    if (report)
+        *report = rep;
+    return PTG_OK;
+}
+
+// ptg_multi_render_to_noise, and with `filter` ptg_multi_render_to_noise_denoised
 static int render_to_noise_on(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
                               const ptg_denoise_params *denoise, bool filter, double *image_rgb,
                               ptg_noise_report *report)
 {
     if (!image_rgb || !target)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_to_noise: NULL image or target");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    int rc = check_frame(m, params);
-    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
-                                 "multi_render_to_noise", ends, &n_ends)))
-        return rc;
+    Passes ps;
     ptg_denoise_params dk{};
-    if (filter && (rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &dk)))
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_target("multi_render_to_noise", target_of(*target), params->samples, ps)) ||
+        (filter && (rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &dk))))
         return rc;
-    m->timed = false;
-    DeviceGuard g;
-    ptg_noise_report rep{};
-    ptg_params p = *params;
-    p.flags |= PTG_FLAG_MOMENTS;
-    if ((rc = ptg_multi_reset_accumulation(m, &p)))
-        return rc;
-    int32_t done = 0;
-    for (int k = 0; k < n_ends; ++k) {
-        unsigned long long st[4];
-        if ((rc = ptg_multi_accumulate(m, &p, done, ends[k])))
-            return rc;
-        done = ends[k];
-        if ((rc = multi_noise(m, &p, done, target->rel_error, target->floor, st)))
-            return rc;
-        rep.samples_done = done;
-        rep.passes = k + 1;
-        rep.pixels = st[3];
-        rep.pixels_over = st[0];
-        rep.pass_samples[k] = done;
-        rep.pass_over[k] = st[0];
-        rep.max_rho = rho_of_bits(st[2]);
-        rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
-        rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
-        if (rep.converged)
-            break;
-    }
-    if (filter) {
-        if ((rc = multi_resolve_filtered(m, &p, done, dk)))
-            return rc;
-    } else {
-        size_t slab_elems = 0;
-        if ((rc = reserve(m, &p, slab_elems)))
-            return rc;
-        const int n = (int)m->shards.size();
-        for (int k = 0; k < n; ++k) {
-            const ptg_params q = shard_params(&p, k, n);
-            if ((rc = ptg_resolve_device(m->shards[k].ctx, &q, done, m->shards[k].slab, m->shards[k].stream)))
-                return rc;
-        }
-        if ((rc = gather_unshard(m, &p, slab_elems)))
-            return rc;
-    }
-    const size_t image_elems = (size_t)p.width * p.height * 3;
-    for (size_t i = 0; i < image_elems; ++i)
-        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
-    if (report)
-        *report = rep;
-    return PTG_OK;
+    return noise_frame_on(m, params, ps, target, filter ? &dk : nullptr, image_rgb, report);
 }
 
 int ptg_multi_render_to_noise(ptg_multi *m, const ptg_params *params, const ptg_noise_target *target,
@@ -1107,15 +1061,11 @@ static int render_adaptive_on(ptg_multi *m, const ptg_params *params, const ptg_
 {
     if (!image_rgb || !target)
         return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_adaptive: NULL image or target");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    int rc = check_frame(m, params);
-    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
-                                 "multi_render_adaptive", ends, &n_ends)))
-        return rc;
-    if (target->dilate < 0 || target->dilate > 8)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "multi_render_adaptive: dilate must be in [0, 8]");
+    Passes ps;
     ptg_denoise_params dk{};
-    if (filter && (rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &dk)))
+    int rc = check_frame(m, params);
+    if (rc || (rc = check_target("multi_render_adaptive", target_of(*target), params->samples, ps)) ||
+        (filter && (rc = ptg_denoise_params_for_(&m->cam, params->width, params->height, denoise, &dk))))
         return rc;
     m->timed = false;
     DeviceGuard g;
@@ -1129,34 +1079,9 @@ static int render_adaptive_on(ptg_multi *m, const ptg_params *params, const ptg_
         MULTI_HIP(hipSetDevice(s.id));
         MULTI_HIP(hipMemsetAsync(s.stats + 6, 0, 4 * sizeof(unsigned long long), s.stream));
     }
-    if ((rc = ptg_multi_reset_accumulation(m, &p)) || (rc = multi_set_mask(m, &p, nullptr)))  // pass 0: every pixel
+    if ((rc = adaptive_passes(MultiSteps{m, p, count}, p, ps, *target, rep)))
         return rc;
-    unsigned long long active = (unsigned long long)p.width * p.height;
-    int32_t done = 0;
-    for (int k = 0; k < n_ends; ++k) {
-        unsigned long long st[6];
-        const int32_t add = ends[k] - done;
-        if ((rc = multi_accumulate_active(m, &p, add, count)))
-            return rc;
-        done = ends[k];
-        rep.total_samples += active * (unsigned long long)add;
-        if ((rc = multi_select(m, &p, target->rel_error, target->floor, target->dilate, st)))
-            return rc;
-        rep.passes = k + 1;
-        rep.max_samples = done;
-        rep.pixels = st[3];
-        rep.pixels_over = st[0];
-        rep.pass_added[k] = add;
-        rep.pass_over[k] = st[0];
-        rep.pass_active[k] = st[4];
-        rep.max_rho = rho_of_bits(st[2]);
-        rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
-        rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
-        if (rep.converged)
-            break;
-        active = st[4];
-    }
-    if ((rc = filter ? multi_resolve_filtered(m, &p, 0, dk) : multi_resolve_active(m, &p)) ||
+    if ((rc = filter ? multi_resolve_filtered(m, &p, 0, dk) : multi_resolve(m, &p, 0, /*active=*/true)) ||
         (sample_counts && (rc = multi_read_counts(m, &p, sample_counts))))
         return rc;
     if (count) {
@@ -1173,9 +1098,7 @@ static int render_adaptive_on(ptg_multi *m, const ptg_params *params, const ptg_
             for (int i = 0; i < 4; ++i)
                 rep.counters[i] += m->host_stats[(size_t)k * kStats + 6 + i];
     }
-    const size_t image_elems = (size_t)p.width * p.height * 3;
-    for (size_t i = 0; i < image_elems; ++i)
-        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
+    add_image(image_rgb, m->host.data(), (size_t)p.width * p.height * 3);
     if (report)
         *report = rep;
     return PTG_OK;
@@ -1247,17 +1170,10 @@ int ptg_multi_render_denoised(ptg_multi *m, const ptg_params *params, const ptg_
     int rc = check_frame(m, params);
     if (rc || (rc = check_filtered(m, params, params->samples, image_rgb, denoise, "multi_render_denoised", &k)))
         return rc;
-    m->timed = false;
-    DeviceGuard g;
-    ptg_params p = *params;
-    p.flags |= PTG_FLAG_MOMENTS;
-    if ((rc = ptg_multi_reset_accumulation(m, &p)) || (rc = ptg_multi_accumulate(m, &p, 0, p.samples)) ||
-        (rc = multi_resolve_filtered(m, &p, p.samples, k)))
-        return rc;
-    const size_t image_elems = (size_t)p.width * p.height * 3;
-    for (size_t i = 0; i < image_elems; ++i)
-        image_rgb[i] = image_rgb[i] + (double)m->host[i];  // main.cpp:196: image[row] += ...
-    return PTG_OK;
+    Passes ps;
+    ps.ends[0] = params->samples;
+    ps.n = 1;
+    return noise_frame_on(m, params, ps, nullptr, &k, image_rgb, nullptr);
 }
 
 int ptg_multi_frame_device(ptg_multi *m, const ptg_params *params, unsigned long long *counters)
@@ -1397,39 +1313,58 @@ int ptg_multi_inject_gather_fault_(ptg_multi *m, int k)
     return PTG_OK;
 }
 
-int ptg_render_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
-                     const int *devices, int n_devices, double *image_rgb)
+}  // extern "C"
+
+// The one-shot forms: every argument checked before any device work (`args`: the form's own pointers are there;
+// `target` NULL: a form without one), then create, call(m), destroy.
+template <class Call>
+static int one_shot(const std::string &who, bool args, const ptg_sphere *spheres, size_t n_spheres,
+                    const ptg_camera *cam, const ptg_params *params, const int *devices, int n_devices,
+                    const Target *target, bool filtered, const ptg_denoise_params *denoise, Call &&call)
 {
-    if (!params || !image_rgb || !devices || n_devices < 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_multi: NULL argument or no device");
-    int rc = check_frame_params(params);  // argument checks before any device work
+    if (!args || !params || !devices || n_devices < 1 || (filtered && !cam))
+        return fail(PTG_ERR_INVALID_ARGUMENT, who + ": NULL argument or no device");
+    Passes ps;
+    ptg_denoise_params k;
+    int rc = check_frame_params(params);
     if (rc)
+        return rc;
+    if (filtered && !target && params->samples < 2)
+        return fail(PTG_ERR_INVALID_ARGUMENT, who + ": samples must be >= 2 (the variance needs two)");
+    if ((target && (rc = check_target(who, *target, params->samples, ps))) ||
+        (filtered && (rc = ptg_denoise_params_for_(cam, params->width, params->height, denoise, &k))))
         return rc;
     ptg_multi *m = nullptr;
     if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
         return rc;
-    rc = ptg_multi_render(m, params, image_rgb);
+    rc = call(m);
     ptg_multi_destroy(m);
     return rc;
+}
+
+template <class T>
+static Target target_or_none(const T *target)  // (a NULL target fails one_shot's `args`)
+{
+    return target ? target_of(*target) : Target{};
+}
+
+extern "C" {
+
+int ptg_render_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
+                     const int *devices, int n_devices, double *image_rgb)
+{
+    return one_shot("render_multi", image_rgb, spheres, n_spheres, cam, params, devices, n_devices, nullptr, false,
+                    nullptr, [&](ptg_multi *m) { return ptg_multi_render(m, params, image_rgb); });
 }
 
 int ptg_render_to_noise_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
                               const ptg_params *params, const int *devices, int n_devices,
                               const ptg_noise_target *target, double *image_rgb, ptg_noise_report *report)
 {
-    if (!params || !image_rgb || !target || !devices || n_devices < 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise_multi: NULL argument or no device");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    int rc = check_frame_params(params);  // argument checks before any device work
-    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
-                                 "render_to_noise_multi", ends, &n_ends)))
-        return rc;
-    ptg_multi *m = nullptr;
-    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
-        return rc;
-    rc = ptg_multi_render_to_noise(m, params, target, image_rgb, report);
-    ptg_multi_destroy(m);
-    return rc;
+    const Target t = target_or_none(target);
+    return one_shot("render_to_noise_multi", image_rgb && target, spheres, n_spheres, cam, params, devices, n_devices,
+                    &t, false, nullptr,
+                    [&](ptg_multi *m) { return ptg_multi_render_to_noise(m, params, target, image_rgb, report); });
 }
 
 int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
@@ -1437,49 +1372,20 @@ int ptg_render_adaptive_multi(const ptg_sphere *spheres, size_t n_spheres, const
                               const ptg_adaptive_target *target, double *image_rgb, int32_t *sample_counts,
                               ptg_adaptive_report *report)
 {
-    if (!params || !image_rgb || !target || !devices || n_devices < 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_multi: NULL argument or no device");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    int rc = check_frame_params(params);  // argument checks before any device work
-    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
-                                 "render_adaptive_multi", ends, &n_ends)))
-        return rc;
-    if (target->dilate < 0 || target->dilate > 8)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_multi: dilate must be in [0, 8]");
-    ptg_multi *m = nullptr;
-    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
-        return rc;
-    rc = ptg_multi_render_adaptive(m, params, target, image_rgb, sample_counts, report);
-    ptg_multi_destroy(m);
-    return rc;
-}
-
-// the filter's parameters of a one-shot form, checked before any device work
-static int check_denoise_one_shot(const ptg_camera *cam, const ptg_params *params, const ptg_denoise_params *denoise)
-{
-    ptg_denoise_params k;
-    return ptg_denoise_params_for_(cam, params->width, params->height, denoise, &k);
+    const Target t = target_or_none(target);
+    return one_shot("render_adaptive_multi", image_rgb && target, spheres, n_spheres, cam, params, devices, n_devices,
+                    &t, false, nullptr, [&](ptg_multi *m) {
+                        return ptg_multi_render_adaptive(m, params, target, image_rgb, sample_counts, report);
+                    });
 }
 
 int ptg_render_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
                               const ptg_params *params, const int *devices, int n_devices,
                               const ptg_denoise_params *denoise, double *image_rgb)
 {
-    if (!params || !image_rgb || !cam || !devices || n_devices < 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised_multi: NULL argument or no device");
-    int rc = check_frame_params(params);  // argument checks before any device work
-    if (rc)
-        return rc;
-    if (params->samples < 2)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_denoised_multi: samples must be >= 2 (the variance needs two)");
-    if ((rc = check_denoise_one_shot(cam, params, denoise)))
-        return rc;
-    ptg_multi *m = nullptr;
-    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
-        return rc;
-    rc = ptg_multi_render_denoised(m, params, denoise, image_rgb);
-    ptg_multi_destroy(m);
-    return rc;
+    return one_shot("render_denoised_multi", image_rgb, spheres, n_spheres, cam, params, devices, n_devices, nullptr,
+                    true, denoise,
+                    [&](ptg_multi *m) { return ptg_multi_render_denoised(m, params, denoise, image_rgb); });
 }
 
 int ptg_render_to_noise_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
@@ -1487,20 +1393,11 @@ int ptg_render_to_noise_denoised_multi(const ptg_sphere *spheres, size_t n_spher
                                        const ptg_noise_target *target, const ptg_denoise_params *denoise,
                                        double *image_rgb, ptg_noise_report *report)
 {
-    if (!params || !image_rgb || !target || !cam || !devices || n_devices < 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise_denoised_multi: NULL argument or no device");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    int rc = check_frame_params(params);  // argument checks before any device work
-    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
-                                 "render_to_noise_denoised_multi", ends, &n_ends)) ||
-        (rc = check_denoise_one_shot(cam, params, denoise)))
-        return rc;
-    ptg_multi *m = nullptr;
-    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
-        return rc;
-    rc = ptg_multi_render_to_noise_denoised(m, params, target, denoise, image_rgb, report);
-    ptg_multi_destroy(m);
-    return rc;
+    const Target t = target_or_none(target);
+    return one_shot("render_to_noise_denoised_multi", image_rgb && target, spheres, n_spheres, cam, params, devices,
+                    n_devices, &t, true, denoise, [&](ptg_multi *m) {
+                        return ptg_multi_render_to_noise_denoised(m, params, target, denoise, image_rgb, report);
+                    });
 }
 
 int ptg_render_adaptive_denoised_multi(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam,
@@ -1508,23 +1405,12 @@ int ptg_render_adaptive_denoised_multi(const ptg_sphere *spheres, size_t n_spher
                                        const ptg_adaptive_target *target, const ptg_denoise_params *denoise,
                                        double *image_rgb, int32_t *sample_counts, ptg_adaptive_report *report)
 {
-    if (!params || !image_rgb || !target || !cam || !devices || n_devices < 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised_multi: NULL argument or no device");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    int rc = check_frame_params(params);  // argument checks before any device work
-    if (rc || (rc = check_driver(params, target->rel_error, target->floor, target->max_fraction, target->min_samples,
-                                 "render_adaptive_denoised_multi", ends, &n_ends)))
-        return rc;
-    if (target->dilate < 0 || target->dilate > 8)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive_denoised_multi: dilate must be in [0, 8]");
-    if ((rc = check_denoise_one_shot(cam, params, denoise)))
-        return rc;
-    ptg_multi *m = nullptr;
-    if ((rc = ptg_multi_create(spheres, n_spheres, cam, devices, n_devices, &m)))
-        return rc;
-    rc = ptg_multi_render_adaptive_denoised(m, params, target, denoise, image_rgb, sample_counts, report);
-    ptg_multi_destroy(m);
-    return rc;
+    const Target t = target_or_none(target);
+    return one_shot("render_adaptive_denoised_multi", image_rgb && target, spheres, n_spheres, cam, params, devices,
+                    n_devices, &t, true, denoise, [&](ptg_multi *m) {
+                        return ptg_multi_render_adaptive_denoised(m, params, target, denoise, image_rgb, sample_counts,
+                                                                  report);
+                    });
 }
 
 }  // extern "C"

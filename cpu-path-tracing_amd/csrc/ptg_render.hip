@@ -29,6 +29,7 @@
 
 #include "../../include/ptgpu.h"
 #include "bvh_build.hpp"
+#include "frame_passes.hpp"  // add_image: the ADD into the caller's image
 #include "kernel_args.hpp"  // KArgs and the constants shared with the host side
 #include "launch_plan.hpp"  // check_params, fill_launch and their tunables
 #include "pt_device.hpp"
@@ -4370,214 +4371,11 @@ int ptg_render(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *ca
             continue;
         double *dst = image_rgb + (size_t)r * W * 3;
         const size_t off = (size_t)j * W * 3;
-        for (int i = 0; i < W * 3; ++i)  // main.cpp:196: image[row] += ...
-            dst[i] = dst[i] + (f64 ? reinterpret_cast<const double *>(host.data())[off + i]
-                                   : (double)reinterpret_cast<const float *>(host.data())[off + i]);
+        if (f64)
+            ptg_frames::add_image(dst, reinterpret_cast<const double *>(host.data()) + off, (size_t)W * 3);
+        else
+            ptg_frames::add_image(dst, reinterpret_cast<const float *>(host.data()) + off, (size_t)W * 3);
     }
-    return PTG_OK;
-}
-
-int ptg_render_to_noise(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
-                        int device, const ptg_noise_target *target, double *image_rgb, ptg_noise_report *report)
-{
-    if (!image_rgb || !target)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: NULL image or target");
-    int rc = check_params(params);
-    if (rc)
-        return rc;
-    if (!(target->floor > 0.0) || !(target->rel_error >= 0.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: floor must be > 0 and rel_error >= 0");
-    if (!(target->max_fraction >= 0.0 && target->max_fraction < 1.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: max_fraction must be in [0, 1)");
-    if (params->shard_count != 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_to_noise: shard_count must be 1 (one device decides for "
-                                              "the whole frame)");
-    if (params->flags & PTG_FLAG_REFERENCE_F64)
-        return fail(PTG_ERR_UNSUPPORTED, "render_to_noise: progressive passes are fp32 only");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    if ((rc = ptg_noise_schedule(target->min_samples, params->samples, ends, PTG_NOISE_MAX_PASSES, &n_ends)))
-        return rc;
-    ptg_noise_report rep{};
-    ptg_context *ctx = nullptr;
-    if ((rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx)))
-        return rc;
-    ptg_params p = *params;
-    p.flags |= PTG_FLAG_MOMENTS;
-    const int W = p.width, H = p.height;
-    const int slab_rows = shard_slab_rows(H, p.band_rows, 1);
-    const size_t slab_elems = (size_t)slab_rows * W * 3;
-    std::vector<float> host(slab_elems);
-    float *d_slab = nullptr;
-    unsigned long long *d_stats = nullptr;
-    // everything on the null stream, in order; each check's 32 bytes copied back synchronously
-    auto run = [&]() -> int {
-        int r;
-        if (hipMalloc(&d_slab, slab_elems * sizeof(float)) != hipSuccess ||
-            hipMalloc(&d_stats, 4 * sizeof(unsigned long long)) != hipSuccess)
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the image slab failed");
-        if ((r = ptg_reset_accumulation_device(ctx, &p, nullptr)))
-            return r;
-        int32_t done = 0;
-        for (int k = 0; k < n_ends; ++k) {
-            unsigned long long st[4] = {0, 0, 0, 0};
-            PTG_HIP(hipMemsetAsync(d_stats, 0, sizeof(st), nullptr));
-            if ((r = ptg_accumulate_device(ctx, &p, done, ends[k], nullptr, nullptr)))
-                return r;
-            done = ends[k];
-            if ((r = ptg_noise_device(ctx, &p, done, target->rel_error, target->floor, nullptr, nullptr, d_stats,
-                                      nullptr)))
-                return r;
-            PTG_HIP(hipMemcpy(st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
-            rep.samples_done = done;
-            rep.passes = k + 1;
-            rep.pixels = st[3];
-            rep.pixels_over = st[0];
-            rep.pass_samples[k] = done;
-            rep.pass_over[k] = st[0];
-            const uint32_t max_bits = (uint32_t)st[2];
-            float max_rho;
-            std::memcpy(&max_rho, &max_bits, sizeof(max_rho));
-            rep.max_rho = (double)max_rho;
-            rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
-            rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
-            if (rep.converged)
-                break;
-        }
-        if ((r = ptg_resolve_device(ctx, &p, done, d_slab, nullptr)))
-            return r;
-        PTG_HIP(hipMemcpy(host.data(), d_slab, slab_elems * sizeof(float), hipMemcpyDeviceToHost));
-        return PTG_OK;
-    };
-    rc = run();
-    if (d_slab)
-        (void)hipFree(d_slab);
-    if (d_stats)
-        (void)hipFree(d_stats);
-    ptg_context_destroy(ctx);
-    if (rc)
-        return rc;
-    for (int j = 0; j < slab_rows; ++j) {  // shard_count 1: slab row j is output row j
-        if (j >= H)
-            continue;
-        double *dst = image_rgb + (size_t)j * W * 3;
-        for (int i = 0; i < W * 3; ++i)  // main.cpp:196: image[row] += ...
-            dst[i] = dst[i] + (double)host[(size_t)j * W * 3 + i];
-    }
-    if (report)
-        *report = rep;
-    return PTG_OK;
-}
-
-int ptg_render_adaptive(const ptg_sphere *spheres, size_t n_spheres, const ptg_camera *cam, const ptg_params *params,
-                        int device, const ptg_adaptive_target *target, double *image_rgb, int32_t *sample_counts,
-                        ptg_adaptive_report *report)
-{
-    if (!image_rgb || !target)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: NULL image or target");
-    int rc = check_params(params);
-    if (rc)
-        return rc;
-    if (!(target->floor > 0.0) || !(target->rel_error >= 0.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: floor must be > 0 and rel_error >= 0");
-    if (!(target->max_fraction >= 0.0 && target->max_fraction < 1.0))
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: max_fraction must be in [0, 1)");
-    if (target->dilate < 0 || target->dilate > 8)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: dilate must be in [0, 8]");
-    if (params->shard_count != 1)
-        return fail(PTG_ERR_INVALID_ARGUMENT, "render_adaptive: shard_count must be 1 (one device decides for "
-                                              "the whole frame)");
-    if (params->flags & PTG_FLAG_REFERENCE_F64)
-        return fail(PTG_ERR_UNSUPPORTED, "render_adaptive: progressive passes are fp32 only");
-    int32_t ends[PTG_NOISE_MAX_PASSES], n_ends = 0;
-    if ((rc = ptg_noise_schedule(target->min_samples, params->samples, ends, PTG_NOISE_MAX_PASSES, &n_ends)))
-        return rc;
-    ptg_adaptive_report rep{};
-    ptg_context *ctx = nullptr;
-    if ((rc = ptg_context_create(spheres, n_spheres, cam, device, &ctx)))
-        return rc;
-    const ptg_params &p = *params;
-    const int W = p.width, H = p.height;
-    const int slab_rows = shard_slab_rows(H, p.band_rows, 1);
-    const size_t slab_pixels = (size_t)slab_rows * W;
-    const bool count = (p.flags & (PTG_FLAG_COUNT_TESTS | PTG_FLAG_COUNT_NONFINITE)) != 0;
-    std::vector<float> host(slab_pixels * 3);
-    std::vector<int32_t> host_counts(sample_counts ? slab_pixels : 0);
-    float *d_slab = nullptr;
-    int32_t *d_cnt = nullptr;
-    unsigned long long *d_stats = nullptr;  // 6 statistics, then the 4 kernel counters
-    // everything on the null stream, in order; each selection's 48 bytes copied back synchronously
-    auto run = [&]() -> int {
-        int r;
-        if (hipMalloc(&d_slab, slab_pixels * 3 * sizeof(float)) != hipSuccess ||
-            hipMalloc(&d_stats, 10 * sizeof(unsigned long long)) != hipSuccess ||
-            (sample_counts && hipMalloc(&d_cnt, slab_pixels * sizeof(int32_t)) != hipSuccess))
-            return fail(PTG_ERR_OUT_OF_MEMORY, "hipMalloc of the image slab failed");
-        PTG_HIP(hipMemsetAsync(d_stats, 0, 10 * sizeof(unsigned long long), nullptr));
-        unsigned long long *d_seg = count ? d_stats + 6 : nullptr;
-        if ((r = ptg_reset_accumulation_device(ctx, &p, nullptr)) ||
-            (r = ptg_set_active_mask_device(ctx, &p, nullptr, nullptr, nullptr)))  // pass 0: every pixel
-            return r;
-        unsigned long long active = (unsigned long long)W * H;
-        long long units = 0;  // pass 0: the host-side bound
-        int32_t done = 0;
-        for (int k = 0; k < n_ends; ++k) {
-            unsigned long long st[6] = {0, 0, 0, 0, 0, 0};
-            PTG_HIP(hipMemsetAsync(d_stats, 0, sizeof(st), nullptr));
-            const int32_t add = ends[k] - done;
-            if ((r = ptg_accumulate_active_device(ctx, &p, add, units, d_seg, nullptr)))
-                return r;
-            done = ends[k];
-            rep.total_samples += active * (unsigned long long)add;
-            if ((r = ptg_select_active_device(ctx, &p, target->rel_error, target->floor, target->dilate, nullptr,
-                                              d_stats, nullptr)))
-                return r;
-            PTG_HIP(hipMemcpy(st, d_stats, sizeof(st), hipMemcpyDeviceToHost));
-            rep.passes = k + 1;
-            rep.max_samples = done;
-            rep.pixels = st[3];
-            rep.pixels_over = st[0];
-            rep.pass_added[k] = add;
-            rep.pass_over[k] = st[0];
-            rep.pass_active[k] = st[4];
-            const uint32_t max_bits = (uint32_t)st[2];
-            float max_rho;
-            std::memcpy(&max_rho, &max_bits, sizeof(max_rho));
-            rep.max_rho = (double)max_rho;
-            rep.mean_rho = st[3] ? (double)st[1] * 0x1p-20 / (double)st[3] : 0.0;
-            rep.converged = (double)st[0] <= target->max_fraction * (double)st[3];
-            if (rep.converged)
-                break;
-            active = st[4];
-            units = (long long)st[5];  // (> 0: a pixel over the target is active)
-        }
-        if ((r = ptg_resolve_active_device(ctx, &p, d_slab, nullptr)))
-            return r;
-        if (sample_counts) {
-            if ((r = ptg_read_sample_counts_device(ctx, &p, d_cnt, nullptr)))
-                return r;
-            PTG_HIP(hipMemcpy(host_counts.data(), d_cnt, slab_pixels * sizeof(int32_t), hipMemcpyDeviceToHost));
-        }
-        if (count)
-            PTG_HIP(hipMemcpy(rep.counters, d_stats + 6, sizeof(rep.counters), hipMemcpyDeviceToHost));
-        PTG_HIP(hipMemcpy(host.data(), d_slab, slab_pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        return PTG_OK;
-    };
-    rc = run();
-    for (void *q : {(void *)d_slab, (void *)d_stats, (void *)d_cnt})
-        if (q)
-            (void)hipFree(q);
-    ptg_context_destroy(ctx);
-    if (rc)
-        return rc;
-    for (int j = 0; j < H; ++j) {  // shard_count 1: slab row j is output row j
-        double *dst = image_rgb + (size_t)j * W * 3;
-        for (int i = 0; i < W * 3; ++i)  // main.cpp:196: image[row] += ...
-            dst[i] = dst[i] + (double)host[(size_t)j * W * 3 + i];
-        if (sample_counts)
-            std::memcpy(sample_counts + (size_t)j * W, host_counts.data() + (size_t)j * W, (size_t)W * sizeof(int32_t));
-    }
-    if (report)
-        *report = rep;
     return PTG_OK;
 }
 
