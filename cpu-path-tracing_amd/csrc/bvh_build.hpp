@@ -390,7 +390,7 @@ inline uint16_t half_ceil(double x)
     return it == t.end() ? t.back().second : it->second;
 }
 
-// 4-wide tree (ptg_render.hip PTG_BVH_WIDE): each wide node is 4 consecutive
+// 4-wide tree (scan_bvh.hpp bvh_node_step): each wide node is 4 consecutive
 // 16-B records (one 64-B line), one per child -- the child's box and a word:
 // >= 0 the child node's first record, < 0 a leaf (INT_MIN | count << 24 |
 // first).  Box planes are binary16 values on a grid centred on the root box
@@ -488,7 +488,7 @@ struct WideGrid {
     }
 };
 
-// PTG_BVH_Q8 (ptg_render.hip): the same wide node in 48 B -- three 16-B
+// The compact node (scan_bvh.hpp box_hit_sorted): the same wide node in 48 B -- three 16-B
 // loads per node step instead of four (the walk is bound by its load
 // instructions: tools/node_width_bench.hip).  Dwords 0-3: the 4 child words;
 // 4-5: the node's grid origin per axis as binary16 in units of 256 grid

@@ -1,8 +1,9 @@
 // kernel_args.hpp -- what the host hands the render kernels: the KArgs
 // kernel-argument struct and the constants both sides size things by.
 // Filled by scene_prep.hpp (scene fields) and launch_plan.hpp (frame and unit
-// levels), read by the kernels in ptg_render.hip.  The field order and types
-// of KArgs are the kernels' kernarg layout: do not reorder.
+// levels), read by the kernels of ptg_render.hip (render_unit.hpp and the
+// device headers around it).  The field order and types of KArgs are the
+// kernels' kernarg layout: do not reorder.
 #pragma once
 
 #include <cmath>

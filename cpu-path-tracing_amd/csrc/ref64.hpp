@@ -2,7 +2,7 @@
 // (PTG_FLAG_REFERENCE_F64): the reference's per-pixel algorithm in double
 // precision on the GPU, operation for operation.
 //
-// The fp32 megakernel (ptg_render.hip) restates the reference with fp32
+// The fp32 megakernel (render_unit.hpp) restates the reference with fp32
 // reformulations (anchored walls, Lagrange discriminant, fraction compares,
 // deterministic sqrt/rsqrt sequences: DESIGN.md section 2).  This mode runs
 // instead the reference's own double arithmetic as src/main.cpp and the pt

@@ -452,10 +452,13 @@ class MultiContext:
         return (out, counts) if sample_counts else out
 
 
-# every csrc file ptg_render.hip includes, but ref64.hpp (the reference-arithmetic kernel) and
-# follow_features.hpp (the followed-feature kernel): neither holds a timed kernel
-KERNEL_SOURCES = ("ptg_render.hip", "pt_device.hpp", "bvh_build.hpp", "kernel_args.hpp", "scene_prep.hpp",
-                  "launch_plan.hpp", "ptg_error.hpp", "sobol_pairs.hpp")
+# ptg_render.hip (its launchers fix the block size and the LDS bytes), the seven headers of device code it
+# includes by topic and the other csrc files the timed kernels and their launch plan are made of; not ref64.hpp
+# (the reference-arithmetic kernel) nor follow_features.hpp (the followed-feature kernel): neither holds a
+# timed kernel (tests/test_kernel_sources.py: no file with device code is left out unnoticed)
+KERNEL_SOURCES = ("ptg_render.hip", "render_config.hpp", "scan_linear.hpp", "scan_bvh.hpp", "shade.hpp",
+                  "render_unit.hpp", "accum_kernels.hpp", "probe_kernels.hpp", "pt_device.hpp", "bvh_build.hpp",
+                  "kernel_args.hpp", "scene_prep.hpp", "launch_plan.hpp", "ptg_error.hpp", "sobol_pairs.hpp")
 
 
 def kernel_source_hash() -> str:

@@ -1,7 +1,7 @@
 // Host-side check of the BVH builder (cpu-path-tracing_amd/csrc/bvh_build.hpp),
 // built and run by tests/test_bvh_builder.py with AddressSanitizer/UBSan.
 // For random scenes it verifies the invariants the GPU traversal relies on
-// (see ptg_render.hip: bvh_node_step):
+// (see scan_bvh.hpp: bvh_node_step):
 //   * every non-huge sphere sits in exactly one leaf, huge spheres in `big`;
 //   * depth-first layout: a node's subtree is the index range [i, skip);
 //     leaves have skip = i + 1; inner nodes' children are i + 1 and the
@@ -209,7 +209,7 @@ static void check_scene(const std::vector<ptg_sphere> &s)
         return;
     }
     check_layout(s, b, b.nodes, 0);
-    // the 8 octant layouts (ptg_render.hip: one per ray-direction octant):
+    // the 8 octant layouts (scan_bvh.hpp bvh_start: one per ray-direction octant):
     // octant 0 is the build order; in octant k every inner node whose split
     // axis has bit k set lists its high-side child first
     for (int oct = 0; oct < 8 && !fails; ++oct) {

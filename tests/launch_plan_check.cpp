@@ -3,7 +3,7 @@
 // and run on the CPU by tests/test_launch_plan.py with AddressSanitizer/UBSan.
 // For every row of a table of frames, shards and progressive passes it fills
 // the plan and verifies what render_kernel relies on when it maps a unit to
-// its level, pixel group and samples (ptg_render.hip: "unit -> level"):
+// its level, pixel group and samples (render_unit.hpp: "unit -> level"):
 //   * lvl_group and lvl_unit are non-decreasing, lvl_group[0] = 0,
 //     lvl_group[n_levels] = n_groups, lvl_unit[n_levels] = n_units;
 //   * every lvl_chunk is in [1, kMaxChunk] (divmod_nv's exact range);

@@ -5,7 +5,7 @@ d.x == 0 exactly in a scene whose only walls are a left/right pair: no axis
 the ray moves toward has a reachable wall plane.  Round 1 then selected a
 missing wall and read the record before the scene array (reproduced with this
 driver: heap-buffer read in test_B via box_walls_B); the kernel had the same
-selection (ptg_render.hip scene_scan).  Both now mask the test; this build
+selection (scan_linear.hpp scene_scan).  Both now mask the test; this build
 runs the driver with ASan + UBSan and requires a clean exit.  The GPU side of
 the same rays: test_gpu_reference.py::test_box_mode_parallel_ray_scene.
 """

@@ -1,5 +1,5 @@
 """BVH kernel wave-level statistics (debug variants PTG_WAVE_STATS=1/2, see
-ptg_render.hip) next to the lane-level counts of the normal counting kernel,
+scan_bvh.hpp and render_unit.hpp) next to the lane-level counts of the normal counting kernel,
 on C5's scene at 1920x1080 with 16 spp.  GPU box: python tools/bvh_wave_stats.py
 [variant ...] (default: the in-tree library, ws1, ws2; a variant named
 <x>ws1 / <x>ws2 is build/libptgpu_<x>ws1.so with PTG_WAVE_STATS=1 / 2)"""

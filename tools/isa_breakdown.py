@@ -2,8 +2,9 @@
 (VERDICT r2 next 5): compiles csrc/ptg_render.hip for gfx950 with -g (line
 info only; same code), takes render_kernel<false, false>'s main loop (the
 outermost loop containing the scene scan), attributes every VALU instruction
-to a source region through its .loc line, and counts opcode classes per
-region.  Usage: python tools/isa_breakdown.py [--asm FILE] [--defs "-D..."]"""
+to a source region through its .loc (file, line) -- the regions are line
+ranges of the device headers, found by the patterns in MARKS -- and counts
+opcode classes per region.  Usage: python tools/isa_breakdown.py [--asm FILE] [--defs "-D..."]"""
 import collections
 import os
 import re
@@ -11,7 +12,11 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "cpu-path-tracing_amd", "csrc", "ptg_render.hip")
+CSRC = os.path.join(ROOT, "cpu-path-tracing_amd", "csrc")
+SRC = os.path.join(CSRC, "ptg_render.hip")
+# the headers ptg_render.hip includes inside its namespace: its device code, by topic
+DEVICE_HEADERS = ("render_config.hpp", "scan_linear.hpp", "scan_bvh.hpp", "shade.hpp", "render_unit.hpp",
+                  "accum_kernels.hpp", "probe_kernels.hpp")
 KERNEL = os.environ.get("ISA_KERNEL", "_ZN12_GLOBAL__N_113render_kernelILb0ELb0ELb0EEEvNS_5KArgsE")  # <kCount, kBvh, kExact>: the default (fast) linear kernel
 
 
@@ -23,24 +28,36 @@ def compile_asm(defs):
     return out
 
 
-def func_lines(path):
-    """source line ranges of the functions/lambdas that matter (by signature search)"""
-    src = open(path).read().splitlines()
+# file of csrc/ -> mark -> the pattern of the mark's line (the first line that matches)
+MARKS = {
+    "scan_linear.hpp": {"scene_scan": r"const LinRec \*scene_scan\(", "test_rec": r"auto test_geo = ",
+                        "test_end": r"auto test_rec = ",
+                        "box_mode": r"if \(PTG_ASSUME_BOX_MODE \|\| A\.box_mode\) \{",
+                        "box_end": r"^        i = A\.end_ax\[2\];"},
+    "shade.hpp": {"shade": r"^__device__ __forceinline__ bool shade\(const ShadeRec \*hit, float t, const float2 \*trig, f3 &o, f3 &d, f3 &T, f3 &E,$",
+                  "dg_block": r"const bool dg_wave = \(__ballot\(1\) & ~__ballot\(mat == PTG_SPECULAR\)\) != 0ull;",
+                  "spec_block": r"if \(spec\) \{  // main.cpp:60"},
+    "render_unit.hpp": {"camera_ray": r"void camera_ray\(", "camera_end": r"int out_row_of\(",
+                        "ray_of": r"auto ray_of = ", "flush": r"auto flush = ", "refill": r"auto refill = "},
+}
+
+
+def func_lines():
+    """file -> mark -> source line of the functions/lambdas that matter (by signature search)"""
     marks = {}
-    pats = {"camera_ray": r"void camera_ray\(", "scene_scan": r"const LinRec \*scene_scan\(",
-            "test_rec": r"auto test_geo = ", "test_end": r"auto test_rec = ", "box_mode": r"if \(PTG_ASSUME_BOX_MODE \|\| A\.box_mode\) \{", "axis_groups": r"\} else \{\s*$",
-            "box_end": r"^        i = A\.end_ax\[2\];", "shade": r"^__device__ __forceinline__ bool shade\(const ShadeRec \*hit, float t, const float2 \*trig, f3 &o, f3 &d, f3 &T, f3 &E,$",
-            "dg_block": r"const bool dg_wave = \(__ballot\(1\) & ~__ballot\(mat == PTG_SPECULAR\)\) != 0ull;", "spec_block": r"if \(spec\) \{  // main.cpp:60",
-            "ray_of": r"auto ray_of = ", "begin": r"auto begin = ", "flush": r"auto flush = ",
-            "refill": r"auto refill = ", "main_loop": r"for \(;;\) \{"}
-    for i, l in enumerate(src, 1):
-        for k, p in pats.items():
-            if k not in marks and re.search(p, l):
-                marks[k] = i
+    for name, pats in MARKS.items():
+        m = marks[name] = {}
+        for i, l in enumerate(open(os.path.join(CSRC, name)).read().splitlines(), 1):
+            for k, p in pats.items():
+                if k not in m and re.search(p, l):
+                    m[k] = i
+        missing = sorted(set(pats) - set(m))
+        if missing:
+            sys.exit(f"{name}: no line matches the mark(s) {missing}")
     return marks
 
 
-def region_of(f, line, m):
+def region_of(f, line, marks):
     if f == "pt_device.hpp":
         if 33 <= line <= 44: return "rsqrt (normalise)"
         if 52 <= line <= 68: return "sqrt (Goldschmidt)"
@@ -49,30 +66,38 @@ def region_of(f, line, m):
         if 110 <= line <= 117: return "RNG draws"
         if 127 <= line <= 136: return "sin/cos table"
         return "vector math (dot/cross)"
-    if f != "ptg_render.hip":
+    if f not in DEVICE_HEADERS:
         return "other (" + f + ")"
-    if m["camera_ray"] <= line < m["scene_scan"]:
-        return "camera ray"
-    if m["test_rec"] <= line < m["test_end"]:
-        return "sphere test (test_rec)"
-    if m["box_mode"] <= line < m["box_end"]:
-        return "box-mode walls"
-    if m["scene_scan"] <= line < m["scene_scan"] + 200:
-        return "scan control"
-    if m["shade"] <= line < m["dg_block"]:
-        return "shade: hit, emission, RR"
-    if m["dg_block"] <= line < m["spec_block"]:
-        return "shade: diffuse/dielectric"
-    if m["spec_block"] <= line < m["spec_block"] + 12:
-        return "shade: mirror"
-    if m["shade"] + 12 <= line < m["shade"] + 200:
-        return "shade: other"
-    if m["ray_of"] <= line < m["flush"]:
-        return "path start (ray_of/begin)"
-    if m["flush"] <= line < m["refill"]:
-        return "path end (park/flush)"
-    if m["refill"] <= line < m["refill"] + 40:
-        return "refill"
+    m = marks.get(f, {})
+    if line == 0:  # compiler-generated code, whatever file it names
+        return "loop control / other"
+    if f == "scan_linear.hpp":
+        if line < m["scene_scan"]:
+            return "camera ray"  # (comp(): counted with the code before the scan, as it always was)
+        if m["test_rec"] <= line < m["test_end"]:
+            return "sphere test (test_rec)"
+        if m["box_mode"] <= line < m["box_end"]:
+            return "box-mode walls"
+        if line < m["scene_scan"] + 200:
+            return "scan control"
+    elif f == "shade.hpp":
+        if m["shade"] <= line < m["dg_block"]:
+            return "shade: hit, emission, RR"
+        if m["dg_block"] <= line < m["spec_block"]:
+            return "shade: diffuse/dielectric"
+        if m["spec_block"] <= line < m["spec_block"] + 12:
+            return "shade: mirror"
+        if m["shade"] + 12 <= line < m["shade"] + 200:
+            return "shade: other"
+    elif f == "render_unit.hpp":
+        if m["camera_ray"] <= line < m["camera_end"]:
+            return "camera ray"
+        if m["ray_of"] <= line < m["flush"]:
+            return "path start (ray_of/begin)"
+        if m["flush"] <= line < m["refill"]:
+            return "path end (park/flush)"
+        if m["refill"] <= line < m["refill"] + 40:
+            return "refill"
     return "loop control / other"
 
 
@@ -111,7 +136,7 @@ def main():
             tgt = mm.group(1) or mm.group(2)
             if tgt in labels and labels[tgt] < k:
                 loops.append((labels[tgt], k))
-    m = func_lines(SRC)
+    m = func_lines()
     # the main loop: the largest loop
     start, end = max(loops, key=lambda x: x[1] - x[0])
     cur = ("", 0)

@@ -1,4 +1,4 @@
-// Stack depth of the 4-wide BVH walk (ptg_render.hip PTG_BVH_WIDE) on a
+// Stack depth of the 4-wide BVH walk (scan_bvh.hpp bvh_node_step) on a
 // scene dumped by tools/wide_stack_depth.py: camera-like rays (camera
 // position to random points of random spheres) and bounce-like rays (from a
 // sphere's surface, random outward direction), walked with the kernel's
@@ -46,7 +46,7 @@ static bool box_hit_d(const WideGrid &g, const BvhNodeQ &q, const double o[3], c
     return tin <= tout;
 }
 
-// the kernel's float box test (ptg_render.hip box_hit_sorted; 1/d for v_rcp_f32)
+// the kernel's float box test (scan_bvh.hpp box_hit_sorted; 1/d for v_rcp_f32)
 static bool box_hit_f(const WideGrid &g, const BvhNodeQ &q, const double o[3], const double d[3], double tb)
 {
     float s[3], b[3];
